@@ -1,6 +1,12 @@
 """Headline benchmark: images/sec of the Pair-Net inference path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set-up (plans, hipGraph capture, stream
+placement), W warm-up steps, the K timed steps, the outputs of the last timed step when
+`--dump-outputs DIR` is given (see `dump_outputs`), and the JSON line.  Everything else below --
+the secondary legs, the bitwise pipeline check, the roofline / per-kernel figures, the child
+legs and the CPU baseline -- runs only with `--full`.
 
 One "step" = one batch through `PSGTr.simple_test`'s device work (psgtr.py:148-156):
 an 800x1333 image tensor already resident in HBM -> native ResNet-50 -> `CrossHead2.
@@ -22,7 +28,7 @@ bench.py --gpus 8` re-executes through torch.distributed.run); every rank proces
 own images (weak scaling, no data-path collective) and the predicted triplet records are
 all-gathered once per step.
 
-Rank 0 prints ONE JSON line: the contract fields plus
+Rank 0 prints ONE JSON line: the contract fields plus, with `--full`,
   roofline      the dominant kernel's achieved rate, from HIP events recorded around
                 its launches on the launching stream (eager steps right after the timed
                 region)
@@ -113,6 +119,44 @@ def gather_roof(dev, hip, lines_log2=(12, 14, 18), reps=20):
     return res
 
 
+# field names of the per-image tuple `get_bboxes` returns (detector.triplet2Result's order):
+# CrossHead2 and its sibling heads (8 fields), CrossHeadBBox (6 fields, no masks)
+RESULT_FIELDS = {8: ("refine_bboxes", "labels", "rel_pair_idxes", "masks", "pan_results",
+                     "rel_scores", "rel_labels", "rel_dists"),
+                 6: ("refine_bboxes", "labels", "rel_pair_idxes", "rel_scores", "rel_labels",
+                     "rel_dists")}
+DUMP_SAMPLE = 1 << 19     # a field with more elements is written as a seeded sample of this many
+
+
+def dump_outputs(path, results):
+    """--dump-outputs DIR: the result list of the last timed step (what a caller of the timed
+    path receives: one tuple per image of the batch), each field stacked over the batch and
+    written as DIR/<field>.npy -- floating fields as float32, integer and bool fields as
+    float64 (exact).  A field of more than DUMP_SAMPLE elements (the 2R x H0 x W0 masks) is
+    written as DIR/<field>_sample.npy, its elements at DUMP_SAMPLE fixed seeded positions,
+    with the masks' foreground pixel counts beside it (masks_area.npy): a few MB in all."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    names = RESULT_FIELDS.get(len(results[0]),
+                              tuple("field%d" % j for j in range(len(results[0]))))
+    written = {}
+    for j, name in enumerate(names):
+        if not isinstance(results[0][j], torch.Tensor):
+            continue
+        t = torch.stack([r[j] for r in results])
+        dt = torch.float32 if t.is_floating_point() else torch.float64
+        if name == "masks":
+            written["masks_area"] = t.flatten(2).sum(-1, dtype=torch.int64).to(torch.float64)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,),
+                                generator=torch.Generator().manual_seed(0)).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        written[name] = t.to(dt)
+    for name, t in written.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+    return sorted(written)
+
+
 def bench_bbox(args, dev, rank, world):
     """Secondary measurement: the box-trunk sibling
     configs/deformable_detr/cross_r101_vg.py -- image tensor -> ResNet-101 (C3-C5) ->
@@ -185,24 +229,28 @@ def bench_bbox(args, dev, rank, world):
     if world > 1:
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     dt = float(dt)
-    # scheduling only: the last pipelined batch against a plain single-stream call
-    labels, dists = res[0][1].clone(), res[0][5].clone()
-    head.use_graphs = det.backbone.use_graphs = False
-    plain = head.simple_test_bboxes(det.extract_feat(img), metas, rescale=True)
-    torch.cuda.synchronize()
-    check = bool(torch.equal(labels, plain[0][1]) and torch.equal(dists, plain[0][5]))
-    eng = None
-    # per-kernel times of one eager step (HIP events around every launch)
-    step()
-    hip.TIMER = hip.KernelTimer()
-    for _ in range(3):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
+    check, prof = None, None
+    if args.full:
+        # scheduling only: the last pipelined batch against a plain single-stream call
+        labels, dists = res[0][1].clone(), res[0][5].clone()
+        head.use_graphs = det.backbone.use_graphs = False
+        plain = head.simple_test_bboxes(det.extract_feat(img), metas, rescale=True)
+        torch.cuda.synchronize()
+        check = bool(torch.equal(labels, plain[0][1]) and torch.equal(dists, plain[0][5]))
+        eng = None
+        # per-kernel times of one eager step (HIP events around every launch)
         step()
-    agg = hip.TIMER.summary()
-    hip.TIMER = None
-    prof = {k: {"ms_per_step": v["ms"] / 3, "launches_per_step": v["launches"] // 3,
-                "tflops": v["flops"] / v["ms"] * 1e-9 if v["ms"] else 0.0,
-                "gbs": v["bytes"] / v["ms"] * 1e-6 if v["ms"] else 0.0}
-            for k, v in sorted(agg.items(), key=lambda kv: -kv[1]["ms"])}
+        hip.TIMER = hip.KernelTimer()
+        for _ in range(3):
+            step()
+        agg = hip.TIMER.summary()
+        hip.TIMER = None
+        prof = {k: {"ms_per_step": v["ms"] / 3, "launches_per_step": v["launches"] // 3,
+                    "tflops": v["flops"] / v["ms"] * 1e-9 if v["ms"] else 0.0,
+                    "gbs": v["bytes"] / v["ms"] * 1e-6 if v["ms"] else 0.0}
+                for k, v in sorted(agg.items(), key=lambda kv: -kv[1]["ms"])}
     out = {"metric": "images/sec (whole node), CrossHeadBBox 300-proposal 800x1333, MI355X",
            "value": world * B * args.steps / dt, "unit": "images/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
@@ -220,10 +268,11 @@ def bench_bbox(args, dev, rank, world):
                            "(encoder, proposals) of consecutive images alternate between %d streams, "
                            "their query chains run on %d more" % (depth, args.a_streams,
                                                                   depth - args.a_streams)},
-           "pipeline_check": "labels / rel_dists of the last pipelined image are bitwise the eager "
+           "pipeline_check": None if check is None else
+                             "labels / rel_dists of the last pipelined image are bitwise the eager "
                              "single-stream result" if check else "MISMATCH",
            "kernel_profile": prof}
-    if not check:
+    if check is False:
         raise SystemExit("pipelined result differs from the eager one")
     import torch.distributed as dist
     if world > 1 and dist.is_initialized():
@@ -298,6 +347,12 @@ def main():
                          "script in a child process)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the bitwise pipeline check, the secondary "
+                         "legs, the roofline / per-kernel figures, the child legs and the CPU "
+                         "baseline (--no-extras / --no-sub-legs / --no-cpu-baseline trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result tuples of the last timed step as DIR/<field>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -428,6 +483,7 @@ def main():
     gatherer = collector.gatherer if collector is not None else None
 
     def gather(res, sub_pos, obj_pos):
+        last_res[0] = res            # (every result passes here: --dump-outputs takes the last)
         if collector is not None and res is not None:
             src = getattr(res, "pipeline_stream", None) if engine is not None else None
             collector.add(TripletBatch(
@@ -468,6 +524,7 @@ def main():
 
     nstep = [0]            # steps issued so far (selects the pool image)
     on_result = [None]     # optional consumer of every result list (legs below)
+    last_res = [None]      # the newest result list
 
     def drain():
         if engine is not None:
@@ -504,6 +561,7 @@ def main():
     # above leaves the GPU idle for tens of ms (host-side calibration bookkeeping, the GC
     # pass), and the first 20 steps after >= 50 ms of idle take 3 % longer than the same 20
     # steps issued back to back (tools/filldrain_probe.py: 101.1 vs 97.9 ms) ----
+    nstep[0] = 0           # (the images of the warm-up and timed steps depend on W and K alone)
     for _ in range(args.warmup):
         step()
     drain()
@@ -540,11 +598,17 @@ def main():
         t = torch.tensor([host_ms], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         host_ms = float(t.item())
+    if args.dump_outputs and rank == 0:
+        res = last_res[0]
+        if hasattr(res, "panoptic_jobs"):   # (the caller's D2H point: detector.simple_test)
+            head.panoptic_status(res)
+        dump_outputs(args.dump_outputs, res)
 
+    # ---- everything below runs with --full only ----
     # ---- the pipelined schedule only reorders launches: for EVERY image of the pool the
     # pipelined result must equal, bit for bit, what one eager single-stream call gives ----
     pipeline_check = None
-    if rank == 0 and engine is not None and world == 1:
+    if args.full and rank == 0 and engine is not None and world == 1:
         n_img = len(pool) if args.path == "image" else 1
         got = []
         on_result[0] = lambda res: got.append(
@@ -580,7 +644,7 @@ def main():
     # 6 MB of bits) into a ring of pinned host buffers, Results built on the host for every
     # image ----
     simple_test = None
-    if rank == 0 and world == 1 and engine is not None and args.path == "image":
+    if args.full and rank == 0 and world == 1 and engine is not None and args.path == "image":
         from pairnet_amd import ResultStreamer
         streamer = ResultStreamer(head, ring=args.depth + 2)
         made = [0, None]
@@ -636,8 +700,8 @@ def main():
     # from this run's backbone + head and its calibrated pipeline.  What the loop costs on top
     # of the bare step() loop above is the difference to the headline. ----
     product_loop = None
-    if rank == 0 and world == 1 and engine is not None and args.path == "image" and B == 1 \
-            and args.head == "pairnet" and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and engine is not None and args.path == "image" \
+            and B == 1 and args.head == "pairnet" and not args.no_extras:
         from pairnet_amd import PSGTr
         from pairnet_amd.dist import multi_gpu_test
         det = PSGTr.from_parts(backbone, head)
@@ -787,7 +851,7 @@ def main():
 
     # ---- secondary: the head alone on the resident pyramid (round 1's headline) ----
     head_only = None
-    if args.path == "image" and world == 1:
+    if args.full and args.path == "image" and world == 1:
         # (its own pipeline: without a backbone in front one stage-A stream and two chain
         # streams are the faster schedule for the head alone)
         n = min(args.steps, 100)
@@ -824,7 +888,7 @@ def main():
     # test pipeline (resize keep-ratio / normalise / pad, pairnet.py:310-331) as one kernel in
     # front of the backbone, on the same stream ----
     from_decoded = None
-    if args.path == "image" and world == 1 and B == 1:
+    if args.full and args.path == "image" and world == 1 and B == 1:
         from pairnet_amd import TestPipeline
         from pairnet_amd.preprocess import rescale_size
         h0, w0 = round(H / sf), round(W / sf)
@@ -915,7 +979,7 @@ def main():
     # of the timed region above because ~150 event pairs per step cost host time there. ----
     timer = dominant = prof = None
     nprof = min(args.steps, 10)
-    if rank == 0:
+    if args.full and rank == 0:
         head.use_graphs = False   # events need eager, single-stream launches
         if backbone is not None:
             backbone.use_graphs = False
@@ -1135,7 +1199,7 @@ def main():
 
     # (single-GPU runs only: the extras re-enter step(), whose triplet all-gather is a
     # collective the other ranks would not be in)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         def timeit(fn, n=5):
             fn()
             torch.cuda.synchronize()
@@ -1401,7 +1465,7 @@ def main():
             except Exception as e:  # pragma: no cover
                 out["breakdown_ms"]["backbone_torch_error"] = repr(e)
 
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_sub_legs and \
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not args.no_sub_legs and \
             args.head == "pairnet" and args.path == "image" and (H, W) == (800, 1333) and not swin:
         # BASELINE configs[3] ("Swin-L + Mask2Former, 200 object queries", one image per GPU) and
         # the box-trunk sibling, each as a short run of this script in a child process (its own
@@ -1409,8 +1473,8 @@ def main():
         # for the configurations the headline does not cover
         def leg(extra, steps=16, warm=6):
             cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps),
-                   "--warmup", str(warm), "--no-extras", "--no-cpu-baseline", "--no-sub-legs",
-                   "--gemm-arithmetic", args.gemm_arithmetic] + extra
+                   "--warmup", str(warm), "--full", "--no-extras", "--no-cpu-baseline",
+                   "--no-sub-legs", "--gemm-arithmetic", args.gemm_arithmetic] + extra
             t0 = time.perf_counter()
             try:
                 cp = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
@@ -1445,7 +1509,7 @@ def main():
             out["training_step"] = repr(e)
 
     gc.enable()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle.head import OracleCrossHead2
         from oracle.baseline_head import OracleCrossHeadBaseline
         from oracle.psgtr_head2 import OraclePSGTrHead2

@@ -439,7 +439,7 @@ def test_bench_two_ranks_complete_and_report_whole_job_rate():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["PAIRNET_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6",
-           "--warmup", "3", "--height", "256", "--width", "320"]
+           "--warmup", "3", "--height", "256", "--width", "320", "--full"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -463,7 +463,7 @@ def test_bench_bbox_head_two_ranks():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["PAIRNET_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--head", "bbox", "--gpus", "2",
-           "--steps", "5", "--warmup", "3", "--height", "320", "--width", "416"]
+           "--steps", "5", "--warmup", "3", "--height", "320", "--width", "416", "--full"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

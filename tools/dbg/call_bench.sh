@@ -1,11 +1,13 @@
 #!/bin/sh
 # one GPU call: tests given as $1 (pytest selection), the full bench line + a readable digest
+# (files go to $OUT)
+: "${OUT:?set OUT to an output directory}"; mkdir -p "$OUT"; export OUT
 python -m pytest $1 -x -q -m gpu 2>&1 | tail -4
-python bench.py --no-cpu-baseline $2 2>gpurun_out/bench_err.txt | tail -1 > gpurun_out/bench_latest.json
-tail -c 400 gpurun_out/bench_err.txt
+python bench.py --full --no-cpu-baseline $2 2>"$OUT/bench_err.txt" | tail -1 > "$OUT/bench_latest.json"
+tail -c 400 "$OUT/bench_err.txt"
 python - <<'PY'
-import json
-d = json.load(open("gpurun_out/bench_latest.json"))
+import json, os
+d = json.load(open(os.path.join(os.environ["OUT"], "bench_latest.json")))
 print("HEADLINE", d["value"], d["ms_per_step"], "| fp32 encoder:", (d.get("fp32_mfma_encoder") or {}).get("images_per_s"))
 r = d.get("roofline") or {}
 print("dominant", r.get("kernel"), r.get("frac"), r.get("ms_per_step"))

@@ -8,7 +8,7 @@ ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$ROOT/gpurun_out/pmc"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --steps 3 --warmup 2 --no-pipeline --no-graphs --no-cpu-baseline --no-extras"
+CMD="python $ROOT/bench.py --full --steps 3 --warmup 2 --no-pipeline --no-graphs --no-cpu-baseline --no-extras"
 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o fetch -- $CMD > "$OUT/fetch.log" 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o write -- $CMD > "$OUT/write.log" 2>&1
 # matrix-pipe utilisation: SQ counters only, their own pass
