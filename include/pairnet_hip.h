@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PN_ABI_VERSION 28
+#define PN_ABI_VERSION 29
 int pn_abi_version(void);
 
 /* ------------------------------------------------------------------------- *
@@ -822,6 +822,36 @@ int pn_subsample2_f32(const float* in, float* out, int B, int Hi, int Wi, int Ho
                       void* stream);
 /* x[r][0:cols] *= s[r] */
 int pn_scale_rows_f32(float* x, const float* s, int64_t rows, int64_t cols, void* stream);
+/* Swin backbone backward (csrc/swin_grad.hip; pair-net_amd/grad.py SwinBackboneGrad): the last stage
+ * that configs/mask2former/pairnet_swinb.py:201-240 trains (frozen_stages=3: stages.3 + norm3 of
+ * [3P] mmdet SwinTransformer).
+ * LayerNorm backward over rows of any width C % 4 == 0, C <= 3072 (SwinBlock norm1 / norm2, the
+ * stage's output norm3) from the saved INPUT x: dx, and gxhat = dy * xhat whose column sum is
+ * d weight (d bias = column sum of dy).  Row strides in floats. */
+int pn_layernorm_rows_bwd_f32(const float* dy, int64_t lddy, const float* x, int64_t ldx,
+                              const float* gamma, float* dx, int64_t lddx, float* gxhat,
+                              int64_t ldg, int64_t rows, int C, float eps, void* stream);
+/* Exact (erf) GELU of the Swin FFN (mmcv FFN act_cfg=dict(type='GELU'), between ffn.layers.0.0 and
+ * ffn.layers.1): y = x Phi(x), and its backward dx = dy (Phi(x) + x phi(x)) from the saved
+ * pre-activation x (dx may alias dy). */
+int pn_gelu_f32(const float* x, float* y, int64_t n, void* stream);
+int pn_gelu_bwd_f32(const float* dy, const float* x, float* dx, int64_t n, void* stream);
+/* Backward of pn_window_attention_f32 (ShiftWindowMSA / WindowMSA.forward), same operand
+ * conventions: qkv [B*H*W][ldqkv] and qkv_bias (padding tokens' q/k/v), bias_table [heads][(2ws-1)^2],
+ * dout [B*H*W][lddo] the gradient of the attention output, out [B*H*W][ldo] the saved output (or
+ * NULL: recomputed) ->
+ *   dqkv [B*Hp*Wp][lddqkv]: d q | d k | d v over the PADDED, un-shifted grid (Hp, Wp: H, W rounded
+ *     up to multiples of ws).  Every row is written, padding rows included: the reference pads
+ *     before the qkv Linear, so their gradient belongs to d qkv.bias (the column sum over all rows);
+ *   dtable_part [B][nwin][heads][(2ws-1)^2]: the bias-table gradient of each (image, window, head),
+ *     nwin = (Hp/ws)(Wp/ws), to be column-summed (pn_colsum_f32) in a fixed order.
+ * No atomics: bitwise reproducible.  ws*ws <= 169; needs (2 N 32 + N (N|1) + (2ws-1)^2 + 3N) * 4
+ * bytes of LDS per workgroup (N = ws^2; 163 388 at ws = 13). */
+int pn_window_attention_bwd_f32(const float* qkv, int64_t ldqkv, const float* qkv_bias,
+                                const float* bias_table, const float* dout, int64_t lddo,
+                                const float* out, int64_t ldo, float* dqkv, int64_t lddqkv,
+                                float* dtable_part, int B, int H, int W, int C, int heads, int ws,
+                                int shift, float scale, void* stream);
 /* out[ci][T-1-t][co] = in[co][t][ci]: a "same" convolution's weight as its data gradient reads it */
 int pn_conv_weight_bwd_layout_f32(const float* in, float* out, int Co, int T, int Ci, void* stream);
 

@@ -536,18 +536,25 @@ class PSGTr:
                 prepared.append(out)
         return prepared
 
-    def trainer(self, train_backbone=True, **kw):
+    def trainer(self, train_backbone=None, **kw):
         """The per-iteration part of the reference's training (tools/train.py:115-241 with mmcv's
         runner: `forward_train` -> `losses.backward()` -> OptimizerHook(grad_clip) -> AdamW, under
         DDP) for this detector: a `pairnet_amd.TailTrainer` over every parameter the reference's R50
-        config trains.  `train_backbone=False` (or a Swin backbone, which has no
-        backward here) freezes the backbone; other keywords go to TailTrainer (lr, lr_mult, group,
-        train_decoder=False / train_pixel_decoder=False for the frozen-detector regimes)."""
+        config trains.  `train_backbone`: None (default) trains a ResNet backbone's
+        stages 2-4 and leaves a Swin backbone frozen; True also trains a Swin backbone's last stage
+        and norm as configs/mask2former/pairnet_swinb.py does (`frozen_stages=3`,
+        `SwinBackboneGrad`); False freezes either.  Other keywords go to TailTrainer (lr, lr_mult,
+        group, drop_path, train_decoder=False / train_pixel_decoder=False for the frozen-detector
+        regimes)."""
         from .backbone import ResNet50Hip
         from .train import TailTrainer
         if type(self.bbox_head) is not CrossHead2:
             raise NotImplementedError("training is built for CrossHead2 only")
-        bb = self.backbone if (train_backbone and isinstance(self.backbone, ResNet50Hip)) else None
+        if train_backbone is None:
+            train_backbone = isinstance(self.backbone, ResNet50Hip)
+        bb = self.backbone if (train_backbone and isinstance(self.backbone, (ResNet50Hip,
+                                                                            SwinTransformerHip))) \
+            else None
         kw.setdefault("train_decoder", True)
         kw.setdefault("train_pixel_decoder", True)
         if not (kw["train_decoder"] and kw["train_pixel_decoder"]):

@@ -32,7 +32,7 @@ import torch
 
 from . import hip
 
-__all__ = ["RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad"]
+__all__ = ["RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad"]
 
 
 class RelationTailGrad:
@@ -1008,4 +1008,207 @@ class BackboneGrad(RelationTailGrad):
             dx = None if first else dxin.view(B, hi, wi, cin)
             ready(self.group_end[p[:-1]])
         ready(self.flat_numel)
+        return grads
+
+
+class SwinBackboneGrad(RelationTailGrad):
+    """The Swin backbone's trainable part -- the two blocks of the last stage and its output norm
+    (configs/mask2former/pairnet_swinb.py:201-240, `frozen_stages=3`: mmdet's `_freeze_stages`
+    fixes patch_embed, stages 0-2 with their patch merging, and norm0-norm2) -- taped and
+    differentiated from the stage-4 input tokens to C5:
+
+        tape = SwinBackboneGrad(swin)             # swin.frozen_stages must be 3
+        x4 = tape.stage_input()                   # [B, h4, w4, C4] of the backbone's last forward
+        c5 = tape.forward(x4, keep=None)          # channel-last [B, h4, w4, C4]
+        grads = tape.backward(d_c5)               # d_c5 [B, C4, h4, w4], e.g. PixelDecoderGrad's dfeats[0]
+
+    Per block: norm1 -> qkv -> (shifted-)window attention -> proj (+ residual) -> norm2 -> FFN
+    Linear -> GELU -> FFN Linear (+ residual), on the exact-fp32 kernels whatever
+    `swin.gemm_arithmetic` says.  The attention backward (`pn_window_attention_bwd_f32`) returns
+    the qkv gradient over the PADDED token grid: the reference pads the normalised map before the
+    qkv Linear, so the padding tokens' gradient belongs to `qkv.bias`.  `keep` [blocks, 2, B]:
+    mmdet's DropPath as per-image scale factors of the (attention, FFN) residual branches (0 or
+    1 / (1 - p)), None for none.  Gradients are named like the backbone's state dict; the bias
+    table's in the reference layout [(2ws-1)^2, heads]."""
+
+    BLOCK_PARAMS = ("norm1.weight", "norm1.bias", "attn.w_msa.relative_position_bias_table",
+                    "attn.w_msa.qkv.weight", "attn.w_msa.qkv.bias", "attn.w_msa.proj.weight",
+                    "attn.w_msa.proj.bias", "norm2.weight", "norm2.bias", "ffn.layers.0.0.weight",
+                    "ffn.layers.0.0.bias", "ffn.layers.1.weight", "ffn.layers.1.bias")
+    EPS = 1e-5
+
+    def __init__(self, backbone, flat=None, base=0):
+        if getattr(backbone, "frozen_stages", -1) != len(backbone.depths) - 1:
+            raise NotImplementedError("SwinBackboneGrad trains the last stage only (frozen_stages=%d, "
+                                      "the reference's config); got frozen_stages=%s"
+                                      % (len(backbone.depths) - 1,
+                                         getattr(backbone, "frozen_stages", -1)))
+        S = len(backbone.depths) - 1
+        if S not in backbone.out_indices:
+            raise NotImplementedError("the last stage must be an output stage (norm%d)" % S)
+        if backbone.device is None or backbone.device.type != "cuda":
+            raise RuntimeError("SwinBackboneGrad needs a backbone on an MI355X (.to('cuda:N'))")
+        if backbone.w is None:
+            backbone._pack()
+        self.head, self.dev, self.t = backbone, backbone.device, None
+        self.S = S
+        self.C, self.heads, self.ws = backbone.num_features[S], backbone.num_heads[S], backbone.ws
+        self._build_layout(backbone, flat, base)
+
+    @staticmethod
+    def param_groups(backbone):
+        S = len(backbone.depths) - 1
+        groups = [("norm%d" % S, ["norm%d.weight" % S, "norm%d.bias" % S])]
+        for j in reversed(range(backbone.depths[S])):
+            p = "stages.%d.blocks.%d." % (S, j)
+            groups.append((p[:-1], [p + n for n in SwinBackboneGrad.BLOCK_PARAMS]))
+        return groups
+
+    @torch.no_grad()
+    @hip.on_device
+    def stage_input(self):
+        """The last stage's input tokens [B, h, w, C] of the backbone's most recent forward: its
+        plan's patch-merge buffer still holds the merged rows of the stage before (the last stage
+        has no patch merging), so the frozen reduction GEMM is run on them once more."""
+        bb = self.head
+        pl = getattr(bb, "_last_plan", None)
+        if pl is None:
+            raise RuntimeError("stage_input() needs a forward of the backbone first")
+        B, S = bb._last_batch, self.S
+        C2 = bb.num_features[S - 1]
+        h, wd = pl.hw[S]
+        n = B * h * wd
+        x4 = self._E(B, h, wd, self.C)
+        hip.linear(pl.merged[:n * 4 * C2].view(n, 4 * C2),
+                   bb.w["stages.%d.downsample.reduction.weight" % (S - 1)], None, x4.view(n, self.C),
+                   scratch=pl.scratch)
+        return x4
+
+    def _branch(self, out, x, keep):
+        """out (the branch's rows) <- x + keep[image] * out"""
+        if keep is not None:
+            hip.scale_rows(out, keep)
+        hip.add_periodic(out, x, out)
+
+    @torch.no_grad()
+    @hip.on_device
+    def forward(self, x4, keep=None):
+        bb, w, E = self.head, self.head.w, self._E
+        if not (x4.is_cuda and x4.dtype == torch.float32 and x4.dim() == 4 and x4.shape[3] == self.C):
+            raise RuntimeError("x4 must be a [B, h, w, %d] fp32 device tensor" % self.C)
+        B, h, wd, C = x4.shape
+        n, S, ws, nh = B * h * wd, self.S, self.ws, self.heads
+        F = int(bb.mlp_ratio * C)
+        depth = bb.depths[S]
+        if keep is not None:
+            keep = keep.to(self.dev, torch.float32).contiguous()
+            if tuple(keep.shape) != (depth, 2, B):
+                raise ValueError("keep must be [%d blocks, 2 branches, B=%d]" % (depth, B))
+        x = x4.reshape(n, C).clone()
+        blocks = []
+        for j in range(depth):
+            p = "stages.%d.blocks.%d." % (S, j)
+            s = dict(x=x, shift=0 if j % 2 == 0 else ws // 2)
+            s["xn1"] = E(n, C)
+            hip.layernorm_rows(x, w[p + "norm1.weight"], w[p + "norm1.bias"], s["xn1"], self.EPS)
+            s["qkv"] = E(n, 3 * C)
+            hip.linear(s["xn1"], w[p + "attn.w_msa.qkv.weight"], w[p + "attn.w_msa.qkv.bias"], s["qkv"])
+            s["ao"] = E(n, C)
+            hip.window_attention(s["qkv"], w[p + "attn.w_msa.qkv.bias"],
+                                 w[p + "attn.w_msa.relative_position_bias_table"], s["ao"], B, h, wd,
+                                 C, nh, ws, s["shift"])
+            s["x1"] = E(n, C)
+            if keep is None:
+                hip.linear(s["ao"], w[p + "attn.w_msa.proj.weight"], w[p + "attn.w_msa.proj.bias"],
+                           s["x1"], res=x)
+            else:
+                hip.linear(s["ao"], w[p + "attn.w_msa.proj.weight"], w[p + "attn.w_msa.proj.bias"],
+                           s["x1"])
+                self._branch(s["x1"], x, keep[j, 0])
+            s["xn2"] = E(n, C)
+            hip.layernorm_rows(s["x1"], w[p + "norm2.weight"], w[p + "norm2.bias"], s["xn2"], self.EPS)
+            s["pre"], s["hid"] = E(n, F), E(n, F)
+            hip.linear(s["xn2"], w[p + "ffn.layers.0.0.weight"], w[p + "ffn.layers.0.0.bias"], s["pre"])
+            hip.gelu(s["pre"], s["hid"])
+            x = E(n, C)
+            if keep is None:
+                hip.linear(s["hid"], w[p + "ffn.layers.1.weight"], w[p + "ffn.layers.1.bias"], x,
+                           res=s["x1"])
+            else:
+                hip.linear(s["hid"], w[p + "ffn.layers.1.weight"], w[p + "ffn.layers.1.bias"], x)
+                self._branch(x, s["x1"], keep[j, 1])
+            blocks.append(s)
+        c5 = E(B, h, wd, C)
+        hip.layernorm_rows(x, w["norm%d.weight" % S], w["norm%d.bias" % S], c5.view(n, C), self.EPS)
+        self.t = dict(B=B, h=h, w=wd, blocks=blocks, out=x, keep=keep)
+        return c5
+
+    def _lnr_bwd(self, dy, x, prefix, grads, acc=None):
+        """LayerNorm (any width) backward from its saved input; accumulates d weight / d bias;
+        returns dx (+ acc)."""
+        dx, gx = self._E(*x.shape), self._E(*x.shape)
+        hip.layernorm_rows_bwd(dy, x, self.head.w[prefix + "weight"], dx, gx, self.EPS)
+        hip.colsum(gx, grads[prefix + "weight"], accumulate=True)
+        hip.colsum(dy, grads[prefix + "bias"], accumulate=True)
+        if acc is not None:
+            self._acc(dx, acc)
+        return dx
+
+    def _scaled(self, d, keep):
+        if keep is None:
+            return d
+        out = d.clone()
+        hip.scale_rows(out, keep)
+        return out
+
+    @torch.no_grad()
+    @hip.on_device
+    def backward(self, d_c5, on_ready=None, need_dx=False):
+        """d_c5 [B, C, h, w] (any memory format) -> {name: gradient} (views of the flat buffer,
+        valid until the next backward); with `need_dx` also d x4 [B, h, w, C]."""
+        if self.t is None:
+            raise RuntimeError("backward() needs a forward() first")
+        bb, w, E, t = self.head, self.head.w, self._E, self.t
+        B, h, wd, S, ws, nh = t["B"], t["h"], t["w"], self.S, self.ws, self.heads
+        C, n, keep = self.C, B * h * wd, t["keep"]
+        ready = on_ready if on_ready is not None else (lambda end: None)
+        grads = self._zero_grads()
+        dc = d_c5.to(self.dev, torch.float32).permute(0, 2, 3, 1).contiguous().view(n, C)
+        dx = self._lnr_bwd(dc, t["out"], "norm%d." % S, grads)
+        ready(self.group_end["norm%d" % S])
+        hp, wp = -(-h // ws) * ws, -(-wd // ws) * ws
+        nrel = (2 * ws - 1) ** 2
+        for j in reversed(range(bb.depths[S])):
+            p = "stages.%d.blocks.%d." % (S, j)
+            a = p + "attn.w_msa."
+            s = t["blocks"][j]
+            # x_out = x1 + keep * FFN(norm2(x1))
+            dbr = self._scaled(dx, None if keep is None else keep[j, 1])
+            dhid = self._lin_bwd(dbr, s["hid"], w[p + "ffn.layers.1.weight"], grads,
+                                 p + "ffn.layers.1.weight", p + "ffn.layers.1.bias")
+            hip.gelu_bwd(dhid, s["pre"], dhid)
+            dxn2 = self._lin_bwd(dhid, s["xn2"], w[p + "ffn.layers.0.0.weight"], grads,
+                                 p + "ffn.layers.0.0.weight", p + "ffn.layers.0.0.bias")
+            del dhid
+            dx1 = self._lnr_bwd(dxn2, s["x1"], p + "norm2.", grads, acc=dx)
+            # x1 = x + keep * proj(W-MSA(norm1(x)))
+            dbr = self._scaled(dx1, None if keep is None else keep[j, 0])
+            dao = self._lin_bwd(dbr, s["ao"], w[a + "proj.weight"], grads, a + "proj.weight",
+                                a + "proj.bias")
+            dqkv = E(B * hp * wp, 3 * C)
+            part = E(hip.window_partials_rows(B, h, wd, ws), nh * nrel)
+            hip.window_attention_bwd(s["qkv"], w[a + "qkv.bias"], w[a + "relative_position_bias_table"],
+                                     dao, dqkv, part, B, h, wd, C, nh, ws, s["shift"], out=s["ao"])
+            dtab = E(nh, nrel)
+            hip.colsum(part, dtab.view(-1))
+            hip.transpose(dtab, grads[a + "relative_position_bias_table"])    # -> [(2ws-1)^2, heads]
+            hip.colsum(dqkv, grads[a + "qkv.bias"], accumulate=True)         # padding rows included
+            dq_real = dqkv if (hp, wp) == (h, wd) else \
+                dqkv.view(B, hp, wp, 3 * C)[:, :h, :wd].reshape(n, 3 * C)
+            dxn1 = self._lin_bwd(dq_real, s["xn1"], w[a + "qkv.weight"], grads, a + "qkv.weight", None)
+            dx = self._lnr_bwd(dxn1, s["x"], p + "norm1.", grads, acc=dx1)
+            ready(self.group_end[p[:-1]])
+        ready(self.flat_numel)
+        if need_dx:
+            return grads, dx.view(B, h, wd, C)
         return grads

@@ -127,6 +127,12 @@ _SIGS = {
     "pn_dilate2_f32": (C.c_int, [_vp, _vp] + [_i32] * 7 + [_vp]),
     "pn_subsample2_f32": (C.c_int, [_vp, _vp] + [_i32] * 6 + [_vp]),
     "pn_scale_rows_f32": (C.c_int, [_vp, _vp, _i64, _i64, _vp]),
+    "pn_layernorm_rows_bwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64,
+                                            _i32, _f32, _vp]),
+    "pn_gelu_f32": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "pn_gelu_bwd_f32": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
+    "pn_window_attention_bwd_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]
+                                    + [_i32] * 7 + [_f32, _vp]),
     "pn_grad_norm_clip_f32": (C.c_int, [_vp, _i64, _f32, _f32, _vp, _vp, _vp]),
     "pn_adamw_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32,
                                _f32, _i32, _vp, _f32, _vp]),
@@ -191,7 +197,7 @@ _SIGS = {
                                                 _i32, _vp]),
 }
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 28   # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
+ABI_VERSION = 29   # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
 
 _lib = None
 
@@ -1314,6 +1320,65 @@ def scale_rows(x, s):
     assert x.is_contiguous() and x.numel() % rows == 0
     _check(lib().pn_scale_rows_f32(_ptr(x), _ptr(s), rows, x.numel() // rows, _stream()),
            "pn_scale_rows_f32")
+
+
+# ---- Swin backbone backward (csrc/swin_grad.hip; composed in grad.py SwinBackboneGrad) ----------
+def layernorm_rows_bwd(dy, x, gamma, dx, gxhat, eps=1e-5):
+    """LayerNorm backward over 2-D row views of any width C % 4 == 0, C <= 3072, from the saved
+    input x: dx, and gxhat = dy * xhat (its column sum is d weight; d bias: column sum of dy)."""
+    rows, ldx = _rowmajor(x)
+    Cc = x.shape[1]
+    (r1, lddy), (r2, lddx), (r3, ldg) = _rowmajor(dy), _rowmajor(dx), _rowmajor(gxhat)
+    assert r1 == r2 == r3 == rows and dy.shape[1] == dx.shape[1] == gxhat.shape[1] == Cc
+    _check(lib().pn_layernorm_rows_bwd_f32(_ptr(dy), lddy, _ptr(x), ldx, _ptr(gamma), _ptr(dx), lddx,
+                                           _ptr(gxhat), ldg, rows, Cc, eps, _stream()),
+           "pn_layernorm_rows_bwd_f32")
+
+
+def gelu(x, out):
+    """out = exact (erf) GELU of x (contiguous, same size)."""
+    assert x.is_contiguous() and out.is_contiguous() and x.numel() == out.numel()
+    _check(lib().pn_gelu_f32(_ptr(x), _ptr(out), x.numel(), _stream()), "pn_gelu_f32")
+
+
+def gelu_bwd(dy, x, dx):
+    """dx = dy * GELU'(x), x the saved pre-activation; dx may alias dy."""
+    assert dy.is_contiguous() and x.is_contiguous() and dx.is_contiguous() and \
+        dy.numel() == x.numel() == dx.numel()
+    _check(lib().pn_gelu_bwd_f32(_ptr(dy), _ptr(x), _ptr(dx), dy.numel(), _stream()),
+           "pn_gelu_bwd_f32")
+
+
+def window_partials_rows(B, H, W, ws):
+    """Rows of window_attention_bwd's bias-table partials: B * windows of the padded map."""
+    return B * (-(-H // ws)) * (-(-W // ws))
+
+
+def window_attention_bwd(qkv, qkv_bias, table, dout, dqkv, dtable_part, B, H, W, C, heads, ws,
+                         shift, out=None):
+    """Backward of window_attention(): qkv [B*H*W][3C] rows, `table` [heads][(2ws-1)^2], dout
+    [B*H*W][C] (and optionally the saved output `out`) -> dqkv [B*Hp*Wp][3C] over the PADDED,
+    un-shifted grid (every row written, padding rows included) and dtable_part
+    [window_partials_rows(B, H, W, ws)][heads * (2ws-1)^2] (column-sum it for d table)."""
+    n, ldq = _rowmajor(qkv)
+    nd, lddo = _rowmajor(dout)
+    npad, lddq = _rowmajor(dqkv)
+    hp, wp = -(-H // ws) * ws, -(-W // ws) * ws
+    assert n == nd == B * H * W and qkv.shape[1] == 3 * C and dout.shape[1] == C
+    assert npad == B * hp * wp and dqkv.shape[1] == 3 * C
+    nrel = (2 * ws - 1) ** 2
+    assert dtable_part.is_contiguous() and \
+        dtable_part.numel() == window_partials_rows(B, H, W, ws) * heads * nrel
+    ldo = 0
+    if out is not None:
+        no, ldo = _rowmajor(out)
+        assert no == n and out.shape[1] == C
+    flops = 12.0 * B * hp * wp * (ws * ws) * C
+    _check(_launch("k_window_attn_bwd", flops, 40.0 * n * C,
+                   lambda: lib().pn_window_attention_bwd_f32(
+                       _ptr(qkv), ldq, _ptr(qkv_bias), _ptr(table), _ptr(dout), lddo, _ptr(out), ldo,
+                       _ptr(dqkv), lddq, _ptr(dtable_part), B, H, W, C, heads, ws, shift, 32 ** -0.5,
+                       _stream())), "pn_window_attention_bwd_f32")
 
 
 def grad_norm_clip(g, out, scratch, pre=1.0, max_norm=0.0):

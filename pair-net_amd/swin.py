@@ -32,7 +32,8 @@ class SwinTransformerHip:
 
     def __init__(self, embed_dims=128, depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32),
                  window_size=12, mlp_ratio=4, patch_size=4, out_indices=(0, 1, 2, 3),
-                 qkv_bias=True, patch_norm=True, use_abs_pos_embed=False, **unused):
+                 qkv_bias=True, patch_norm=True, use_abs_pos_embed=False, frozen_stages=-1,
+                 drop_path_rate=0.1, **unused):
         if patch_size != 4 or not qkv_bias or not patch_norm or use_abs_pos_embed:
             raise NotImplementedError("patch_size 4, qkv_bias, patch_norm and no absolute "
                                       "position embedding (the reference's configuration)")
@@ -40,6 +41,8 @@ class SwinTransformerHip:
             raise ValueError("depths and num_heads must have one entry per stage")
         self.embed_dims, self.depths, self.num_heads = embed_dims, tuple(depths), tuple(num_heads)
         self.ws, self.mlp_ratio = int(window_size), mlp_ratio
+        # training-only settings (grad.SwinBackboneGrad, train.TailTrainer); inference ignores them
+        self.frozen_stages, self.drop_path_rate = int(frozen_stages), float(drop_path_rate)
         self.out_indices = tuple(out_indices)
         self.num_features = [embed_dims * 2 ** i for i in range(len(depths))]
         for c, nh in zip(self.num_features, self.num_heads):
@@ -268,6 +271,7 @@ class SwinTransformerHip:
         img = img.contiguous()
         B, _, H, W = img.shape
         pl = self._plan(B, H, W, slot)
+        self._last_plan, self._last_batch = pl, B     # (SwinBackboneGrad.stage_input)
         cur = torch.cuda.current_stream(self.device)
         pl.streams[cur.cuda_stream] = cur
         w, ws = self.w, self.ws

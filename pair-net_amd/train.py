@@ -6,8 +6,10 @@ parameters of `CrossHead2` the loss reaches: by default the Relation Fusion deco
 Matrix Learner (10.2 M), with `train_decoder` the nine masked decoder layers as well (+14.3 M) and
 with `train_pixel_decoder` the pixel decoder's encoder path (+5.3 M), with `backbone=` the ResNet's
 stages 2-4 (+23.2 M; stem, layer1 and BatchNorm frozen as in the reference's config) -- 53.0 M, the
-reference's whole trainable graph.  Without `backbone=` the backbone is frozen (a fine-tuning
-regime); a Swin backbone has no backward here.
+reference's whole trainable graph.  With a `SwinTransformerHip` as `backbone=` the last stage and
+its output norm train instead (`SwinBackboneGrad`; `frozen_stages=3` as in
+configs/mask2former/pairnet_swinb.py:220: 25.2 M for Swin-B, 56.7 M for Swin-L).  Without
+`backbone=` the backbone is frozen (a fine-tuning regime).
 Everything the reference's loss can reach enters through two logits: `loss_r_cls` through
 `rel`, `loss_match` through `importance` (`loss_sub_cls` / `loss_obj_cls` read DETACHED class
 logits, pairnet_head.py:380-390, and train nothing).
@@ -17,7 +19,7 @@ logits, pairnet_head.py:380-390, and train nothing).
 
 Per step: `head.forward` (the inference kernels; hipGraphs if on) -> `head.loss(grads=)` (csrc/
 loss.hip; the two Hungarian assignments on the host as the reference) -> `RelationTailGrad`
-(/ `HeadGrad` / `PixelDecoderGrad` / `BackboneGrad`) forward-with-tape + backward into one flat
+(/ `HeadGrad` / `PixelDecoderGrad` / `BackboneGrad` / `SwinBackboneGrad`) forward-with-tape + backward into one flat
 gradient buffer -> (world > 1) bucketed all-reduce
 overlapped with the backward pass (`dist.GradReducer`) -> global-norm clip coefficient on the
 device -> ONE AdamW launch over the flat parameter buffer that the head's weight dict aliases ->
@@ -30,7 +32,7 @@ import torch
 
 from . import hip
 from .dist import GradReducer
-from .grad import BackboneGrad, HeadGrad, PixelDecoderGrad, RelationTailGrad
+from .grad import BackboneGrad, HeadGrad, PixelDecoderGrad, RelationTailGrad, SwinBackboneGrad
 
 __all__ = ["TailTrainer", "step_lr"]
 
@@ -47,7 +49,7 @@ class TailTrainer:
     def __init__(self, head, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  max_norm=0.1, norm_decay_mult=0.0, lr_mult=None, group=None,
                  bucket_bytes=32 << 20, train_decoder=False, train_pixel_decoder=False,
-                 backbone=None):
+                 backbone=None, drop_path=False, seed=0):
         """`train_decoder`: also train the nine masked decoder layers, `query_feat`, `query_embed`
         and `level_embed` (`HeadGrad`; the reference's `transformer_decoder` group, lr_mult 0.1 by
         default here as in configs/mask2former/pairnet.py:358-363) -- everything of the head behind
@@ -57,13 +59,22 @@ class TailTrainer:
         # `backbone` (a ResNet50Hip): also train its stages 2-4 (`BackboneGrad`; the reference's
         # `backbone` group at lr_mult 0.1, stem / layer1 / BatchNorm frozen as in its config):
         # `step()` then takes the IMAGE tensor.  Its parameters appear as "backbone.<name>".
+        # A SwinTransformerHip trains its last stage + norm (`SwinBackboneGrad`) at lr_mult 0.01
+        # (pairnet_swinb.py:563-571); `drop_path`: mmdet's DropPath on that stage's residual
+        # branches at the rates of the backbone's `drop_path_rate`, drawn per step from a host
+        # generator seeded with `seed` (default off: a deterministic step).
+        from .swin import SwinTransformerHip
         self.backbone = backbone
+        self.swin = isinstance(backbone, SwinTransformerHip)
+        self.drop_path = bool(drop_path) and self.swin
+        self._gen = torch.Generator().manual_seed(int(seed))
         train_pixel_decoder = bool(train_pixel_decoder) or backbone is not None
         self.train_pixel_decoder = bool(train_pixel_decoder)
         self.train_decoder = bool(train_decoder) or self.train_pixel_decoder
         train_decoder = self.train_decoder
         if lr_mult is None:
-            lr_mult = {"transformer_decoder": 0.1, "pixel_decoder": 0.1, "backbone.": 0.1}
+            lr_mult = {"transformer_decoder": 0.1, "pixel_decoder": 0.1,
+                       "backbone.": 0.01 if self.swin else 0.1}
         if head.w is None:
             head._pack()
         # plans captured so far bake the addresses of the weight tensors that are re-homed below
@@ -80,12 +91,13 @@ class TailTrainer:
                 backbone.to(dev)
             if backbone.w is None:
                 backbone._pack()
-        n_bb = BackboneGrad.size_of(backbone) if backbone is not None else 0
+        bb_cls = SwinBackboneGrad if self.swin else BackboneGrad
+        n_bb = bb_cls.size_of(backbone) if backbone is not None else 0
         self.flat_grad = torch.zeros(n_head + n_pd + n_bb, device=dev, dtype=torch.float32)
         self.tape = tape = tape_cls(head, flat=self.flat_grad, base=0)
         self.pd_tape = PixelDecoderGrad(head, flat=self.flat_grad, base=n_head) \
             if self.train_pixel_decoder else None
-        self.bb_tape = BackboneGrad(backbone, flat=self.flat_grad, base=n_head + n_pd) \
+        self.bb_tape = bb_cls(backbone, flat=self.flat_grad, base=n_head + n_pd) \
             if backbone is not None else None
         self.lr, self.wd, self.betas, self.eps, self.max_norm = lr, weight_decay, betas, eps, max_norm
         # name -> (offset in the shared buffer, shape, numel); the class path (cls_embed /
@@ -132,7 +144,10 @@ class TailTrainer:
             offs.append(o)
             lrs.append(0.0 if n in frozen else
                        next((m for key, m in lr_mult.items() if key in n), 1.0))
+            # (a Swin backbone's names -- norm1 / norm2 / norm3, the bias table -- match none of
+            # these: with a `backbone.` custom key mmcv applies no norm_decay_mult to them)
             is_norm = ".norms." in n or "post_norm" in n or ".gn." in n
+            assert not (is_norm and self.swin and n.startswith("backbone.")), n
             wds.append(0.0 if n in frozen else (norm_decay_mult if is_norm else 1.0))
         offs.append(self.n)
         self.seg_off = torch.tensor(offs, dtype=torch.int64, device=dev)
@@ -213,7 +228,31 @@ class TailTrainer:
                     o += h * wd
                 ent[3].copy_(hip.pos8(ent[0]))
         if self.bb_tape is not None:
-            self._refresh_backbone()
+            self._refresh_swin() if self.swin else self._refresh_backbone()
+
+    def _refresh_swin(self):
+        """Rewrite the Swin backbone's packed weights of the trained stage in place: the bias
+        tables transposed to [heads][(2ws-1)^2], the block GEMMs' bf16-plane splits."""
+        w, p = self.backbone.w, self.params
+        for n in self.bb_tape.layout:
+            v = p["backbone." + n]
+            w[n].copy_(v.t() if n.endswith("relative_position_bias_table") else v)
+            if n + ".s3" in w:
+                hip.s3_split(w[n], w[n + ".s3"])
+
+    def _drop_path_keep(self, B):
+        """mmdet DropPath's per-image scale factors [blocks, 2 branches, B] of the trained stage:
+        floor(keep_prob + U[0, 1)) / keep_prob at the block's rate of linspace(0, drop_path_rate,
+        sum(depths))."""
+        bb = self.backbone
+        S = len(bb.depths) - 1
+        dpr = torch.linspace(0, bb.drop_path_rate, sum(bb.depths), dtype=torch.float64)
+        rates = dpr[sum(bb.depths[:S]):].float()                          # [blocks]
+        kp = (1.0 - rates).view(-1, 1, 1)
+        u = torch.rand(len(rates), 2, B, generator=self._gen)
+        keep = torch.floor(kp + u) / kp
+        return keep.pin_memory().to(self.dev, non_blocking=True) if torch.cuda.is_available() \
+            else keep
 
     def _refresh_backbone(self):
         """Re-fold BatchNorm into the trained convolutions and rewrite the backbone's packed
@@ -248,7 +287,7 @@ class TailTrainer:
                 else head._params[n]
             dst.copy_(v.to(dst.device))
         head._packed_version = head._weights_version()     # the packed device weights ARE these values
-        if self.backbone is not None:
+        if self.backbone is not None and hasattr(self.backbone, "_weights_version"):
             self.backbone._packed_version = self.backbone._weights_version()
 
     # ------------------------------------------------------------------
@@ -267,6 +306,10 @@ class TailTrainer:
                                "was built (load_state_dict, parameter update, .to()): build a new one")
         if self.backbone is not None:
             feats = [f.clone(memory_format=torch.preserve_format) for f in self.backbone(feats)]
+            if self.swin:                      # the taped last stage's C5 feeds the head and loss
+                x4 = self.bb_tape.stage_input()
+                keep = self._drop_path_keep(x4.shape[0]) if self.drop_path else None
+                feats[3] = self.bb_tape.forward(x4, keep).permute(0, 3, 1, 2)
         outs = head.forward(feats, img_metas)
         up = {}
         losses = head.loss(*outs, gt_rels, None, gt_labels, gt_masks, img_metas,
@@ -285,7 +328,9 @@ class TailTrainer:
         if self.pd_tape is not None:           # back[0]: d memory tokens (HeadGrad)
             npd = self.pd_tape.flat_numel
             dfeats, _ = self.pd_tape.backward(back[0], on_ready=lambda e: self.reducer.ready(nh + e))
-            if self.bb_tape is not None:       # dfeats: d C5, d C4, d C3
+            if self.bb_tape is not None and self.swin:     # d C5; C2-C4 come from frozen stages
+                self.bb_tape.backward(dfeats[0], on_ready=lambda e: self.reducer.ready(nh + npd + e))
+            elif self.bb_tape is not None:     # dfeats: d C5, d C4, d C3
                 self.bb_tape.forward(feats[0])
                 self.bb_tape.backward(dfeats[2], dfeats[1], dfeats[0],
                                       on_ready=lambda e: self.reducer.ready(nh + npd + e))
