@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PN_ABI_VERSION 29
+#define PN_ABI_VERSION 30
 int pn_abi_version(void);
 
 /* ------------------------------------------------------------------------- *
@@ -153,6 +153,22 @@ int pn_conv2d_nhwc_ex_f32(const float* in, const float* Wp, const float* bias,
                           int Cout, int KH, int KW, int stride, int pad, int flags,
                           float* splitk_scratch /* or NULL */,
                           int64_t splitk_scratch_floats, void* stream);
+/* Output of the FIRST bottleneck of a stage (the one with a projection shortcut) in one launch:
+ *   out = relu(t2 . W3^T + b3 + (x[:, ::stride, ::stride] . Wsc^T + bsc))
+ * x [B][H][W][Cin] (the block input), t2 [B][Ho][Wo][planes] (the 3x3 convolution's output),
+ * Wsc [Cout][Cin], W3 [Cout][planes], out [B][Ho][Wo][Cout], Ho = (H - 1) / stride + 1; Cin and
+ * planes % 32 == 0.  Bit for bit the result of the two launches it replaces (pn_gemm_f32 /
+ * pn_conv2d_nhwc_ex_f32 for the shortcut into `idt`, pn_gemm_f32 with Res = idt for conv3): each
+ * tile contracts the shortcut, keeps acc + bias in registers, clears the accumulators and
+ * contracts conv3; `idt` is not touched.  Where the library's rules would give either of the two
+ * launches, or this one, the split-K path or the skinny kernel, the two launches are issued
+ * instead and `idt` [B][Ho][Wo][Cout] is their intermediate (it may be NULL only if that cannot
+ * happen).  flags: PN_GEMM_RESERVE(n), PN_GEMM_KSPLIT(n). */
+int pn_bottleneck_proj_f32(const float* x, const float* Wsc, const float* bsc, const float* t2,
+                           const float* W3, const float* b3, float* idt, float* out, int B,
+                           int H, int W, int Cin, int planes, int Cout, int stride, int flags,
+                           float* splitk_scratch /* or NULL */, int64_t splitk_scratch_floats,
+                           void* stream);
 /* Stem: relu(conv7x7/2 pad 3 (NCHW RGB image) + bias) -> [B][Ho][Wo][64] channel-last.
  * Wp [64][160] = conv1.weight [64][3][7][7] flattened, zero-padded 147 -> 160. */
 int pn_stem7x7s2_f32(const float* img_nchw, const float* Wp, const float* bias,
@@ -224,6 +240,17 @@ int pn_groupnorm_nhwc_f32(const float* x, const float* gamma, const float* beta,
                           float* y, double* partials, int B, int64_t HW, int C,
                           int G, float eps, int relu, int64_t x_bstride,
                           int64_t y_bstride, void* stream);
+
+/* pn_groupnorm_nhwc_f32 (no ReLU) and the accumulating pn_bilinear_nhwc_f32 behind it in one pass:
+ *   y[b][p][:] = GroupNorm(x)[b][p][:] + bilinear-up(coarse [b][hc][wc][C] -> H x W)[p][:]
+ * (the FPN's top-down add of the pixel decoder, behind pairnet_head.py:262).  The normalised value
+ * and the sample are each rounded as the two kernels round them and then added: bit for bit the
+ * result of the pair, with one read and one write of the H x W map instead of two of each.
+ * `partials` as above; image b of the coarse map starts at coarse + b*coarse_bstride floats. */
+int pn_groupnorm_upadd_nhwc_f32(const float* x, const float* gamma, const float* beta, float* y,
+                                double* partials, const float* coarse, int B, int H, int W,
+                                int hc, int wc, int C, int G, float eps, int64_t x_bstride,
+                                int64_t y_bstride, int64_t coarse_bstride, void* stream);
 
 /* Linear + residual + post-norm of a transformer layer in one launch, N == 256:
  *   y[r][:] = LayerNorm(res[r][:] + x[r][:] W^T + bias) * gamma + beta
@@ -414,6 +441,16 @@ int pn_mask_stencil_gemm_f32(const float* me, int64_t ld_me, int64_t stride_me, 
                              int64_t ld_rows, int64_t stride_rows, uint32_t* bits,
                              int32_t* rowall, int B, int Q, int Nk, int K, int hi, int wi, int ho,
                              int wo, int flags, void* stream);
+
+/* pn_mask_stencil_gemm_f32 without the row copies: `mf` [B][hi*wi][ld_mf] is the full-resolution
+ * mask feature itself, and the loader of each 64-column tile computes the row of (tap, key) the
+ * way pn_bilinear_stencil_rows_f32 does (make_tap of the key's pixel) and reads it in place --
+ * the same K-float rows, hence the same products in the same order and bit-identical bits /
+ * rowall; the 4 Nk x K rows per level are neither written nor kept. */
+int pn_mask_stencil_gather_gemm_f32(const float* me, int64_t ld_me, int64_t stride_me,
+                                    const float* mf, int64_t ld_mf, int64_t stride_mf,
+                                    uint32_t* bits, int32_t* rowall, int B, int Q, int Nk, int K,
+                                    int hi, int wi, int ho, int wo, int flags, void* stream);
 
 /* softmax(q k^T * scale + mask) v per head, flash-style over key chunks
  * (f32 MFMA for both contractions), then a combine pass.

@@ -99,6 +99,10 @@ class ResNet50Hip:
         # K = 64..512 and 4 200- / 1 050-row maps: two to sixteen k-stages per tile and half-empty
         # tile rounds
         self.s3_conv3_min_planes = 0
+        # first block of each stage: projection shortcut and conv3 in one launch (the shortcut
+        # stays in registers as conv3's residual, bit for bit the two launches' result);
+        # False = the shortcut is written to pl.idt by a launch of its own
+        self.fuse_proj_shortcut = True
 
     def _weights_version(self):
         return sum(p._version for p in self._params.values())
@@ -231,7 +235,8 @@ class ResNet50Hip:
         return out
 
     def _plan(self, B, H, W, slot=0):
-        key = (B, H, W, slot, self.conv_algo, self.wino_min_planes, self.s3_conv3_min_planes)   # (a plan's graph bakes them in)
+        key = (B, H, W, slot, self.conv_algo, self.wino_min_planes, self.s3_conv3_min_planes,
+               self.fuse_proj_shortcut)   # (a plan's graph bakes them in)
         if key in self._plans:
             return self._plans[key]
         if self.w is None:
@@ -375,6 +380,16 @@ class ResNet50Hip:
                     hip.conv2d_ex(t1, w[p + "conv2.w"], w[p + "conv2.b"], None, pl.t2[i], B, hi,
                                   wi, planes, planes, 3, 3, stride, 1, relu=True,
                                   scratch=pl.scratch)
+                s3 = self.s3_conv3_min_planes and planes >= self.s3_conv3_min_planes
+                if b == 0 and self.fuse_proj_shortcut and not s3:
+                    # projection shortcut + conv3 (+BN) + ReLU in one launch; pl.idt[i] is only
+                    # the library's workspace where it takes the two-launch form
+                    dst = pl.out[i] if blocks == 1 else pl.ping[i]
+                    hip.bottleneck_proj(x, w[p + "downsample.0.w"], w[p + "downsample.0.b"],
+                                        pl.t2[i], w[p + "conv3.w"], w[p + "conv3.b"], pl.idt[i],
+                                        dst, B, hi, wi, cin, planes, stride, scratch=pl.scratch)
+                    x, cin = dst, planes * 4
+                    continue
                 # shortcut: projection in the first block of a stage, identity after it
                 if b == 0:
                     if stride == 1:
@@ -393,7 +408,7 @@ class ResNet50Hip:
                     dst = pl.out[i]
                 else:
                     dst = pl.ping[i] if idt is not pl.ping[i] else pl.idt[i]
-                if self.s3_conv3_min_planes and planes >= self.s3_conv3_min_planes:
+                if s3:
                     t2 = pl.t2[i].view(-1, planes)
                     hip.s3_split(t2, pl.t2_s3)
                     hip.gemm_s3(pl.t2_s3, w[p + "conv3.w.s3"], t2.shape[0], planes * 4, planes,

@@ -191,7 +191,7 @@ __device__ __forceinline__ void gemm_persistent(const Locator& loc, const int nt
                                    (unsigned)(p.Aadd ? p.ldaadd : p.lda) + kc) * 4u;
       }
     }
-    if constexpr (EPI == 1) {
+    if constexpr (EPI == 1 || EPI == 3) {
       const StencilP& st = loc.st;
       // stencil-mask mode: tile column c <-> (wave sub-tile c / 32, tap (c % 32) / 8, key
       // 16 tn + 8 (c / 32) + c % 8): the four taps of a key sit in ONE wave's 32 columns, 8
@@ -201,7 +201,17 @@ __device__ __forceinline__ void gemm_persistent(const Locator& loc, const int nt
       for (int j = 0; j < NB; ++j) {
         const int c = (tid >> 3) + RPP * j;
         const int key = min(tr.tn * 16 + (c >> 5) * 8 + (c & 7), st.nk - 1);
-        w_off[j] = ((unsigned)(((c >> 3) & 3) * st.nk + key) * (unsigned)p.ldw + kc) * 4u;
+        if constexpr (EPI == 3) {
+          // gather mode: W is the mask feature itself [hi * wi][ldw]; the row of (tap, key) is
+          // the one k_stencil_rows would have copied (tap t <-> (i0,j0), (i0,j1), (i1,j0), (i1,j1))
+          const int t = (c >> 3) & 3;
+          const int oy = key / st.wo, ox = key - oy * st.wo;
+          const Tap ty = make_tap(oy, st.hi, st.ho), tx = make_tap(ox, st.wi, st.wo);
+          const int sy = (t & 2) ? ty.i1 : ty.i0, sx = (t & 1) ? tx.i1 : tx.i0;
+          w_off[j] = ((unsigned)(sy * st.wi + sx) * (unsigned)p.ldw + kc) * 4u;
+        } else {
+          w_off[j] = ((unsigned)(((c >> 3) & 3) * st.nk + key) * (unsigned)p.ldw + kc) * 4u;
+        }
       }
     } else {
 #pragma unroll
@@ -375,6 +385,11 @@ __device__ __forceinline__ void gemm_persistent(const Locator& loc, const int nt
     }
   };
 
+  // EPI == 2 (k_gemm_proj): every tile is contracted twice, TileRef::pi = the phase.  Phase 0
+  // (the projection shortcut, loc.P(0)) leaves acc + bias in `keep`; phase 1 (conv3, loc.P(1))
+  // starts from cleared accumulators and takes `keep` as its residual.
+  static_assert(EPI != 2 || (TM == 1 && TN == 1 && !PN_GEMM_LDS2), "two-phase mode: 32x32 waves, one LDS stage");
+  float keep[EPI == 2 ? 16 : 1];
   TileRef cur = loc(base + slot);
   set_tile(cur);
   load_chunk(0);
@@ -397,10 +412,12 @@ __device__ __forceinline__ void gemm_persistent(const Locator& loc, const int nt
     __syncthreads();
   }
 #endif
-  for (int t = slot; t < cnt; t += per) {
+  for (int t = slot; t < cnt;) {
     const GemmP& p = loc.P(cur.pi);
-    // the tile after this one (clamped: the last tile re-loads its own first chunk, unused)
-    const TileRef nxt = loc(base + min(t + per, cnt - 1));
+    const bool ph0 = EPI == 2 && cur.pi == 0;
+    // the tile after this one (clamped: the last tile re-loads its own first chunk, unused);
+    // two-phase mode: the same tile's second phase
+    const TileRef nxt = ph0 ? TileRef{1, cur.bz, cur.tm, cur.tn} : loc(base + min(t + per, cnt - 1));
     int nk = (p.K + BK - 1) / BK;
     if (p.ksplit > 1) {
       const int sidx = cur.bz % p.ksplit;
@@ -456,12 +473,12 @@ __device__ __forceinline__ void gemm_persistent(const Locator& loc, const int nt
     // accumulator are fetched as 16 independent loads (clamped, unconditional) before
     // any is used: one memory round trip per accumulator instead of sixteen. ----
     const int m0 = cur.tm * BM, n0 = cur.tn * BN;
-    if constexpr (EPI == 1) {
+    if constexpr (EPI == 1 || EPI == 3) {
       const StencilP& st = loc.st;
       // ---- stencil-mask epilogue: blend (the ONE tap_blend every resampling kernel uses),
       // threshold, pack; nothing of C reaches memory.  Lane (half lh, column li): key slot
       // pl = li % 8 of this wave's 8 keys; register r is query row mfma32_row(r, lh). ----
-      static_assert(EPI == 0 || (TM == 1 && TN == 1 && BN == 64), "stencil mode: 64x64 tiles of 32x32 waves");
+      static_assert((EPI != 1 && EPI != 3) || (TM == 1 && TN == 1 && BN == 64), "stencil mode: 64x64 tiles of 32x32 waves");
       const int pl = li & 7;
       const int key0 = cur.tn * 16 + wn * 8;
       const int key = key0 + pl;
@@ -501,7 +518,18 @@ __device__ __forceinline__ void gemm_persistent(const Locator& loc, const int nt
         }
       }
       cur = nxt;
+      t += per;
       continue;
+    }
+    if constexpr (EPI == 2) {
+      if (ph0) {   // the shortcut's value exactly as its own launch would have stored it
+        const int colc = min(n0 + wn * WN + li, p.N - 1);
+        const float bv = p.bias ? p.bias[colc] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) keep[r] = acc[0][0][r] + bv;
+        cur = nxt;
+        continue;
+      }
     }
     float* __restrict__ C = p.C + (int64_t)cur.bz * p.sC;
     const float* __restrict__ Res = p.Res ? p.Res + (int64_t)cur.bz * p.sRes : nullptr;
@@ -515,7 +543,10 @@ __device__ __forceinline__ void gemm_persistent(const Locator& loc, const int nt
       for (int mi = 0; mi < TM; ++mi) {
         const int rbase = m0 + wm * WM + mi * 32;
         float rv[16];
-        if (Res) {
+        if constexpr (EPI == 2) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) rv[r] = keep[r];
+        } else if (Res) {
 #pragma unroll
           for (int r = 0; r < 16; ++r)
             rv[r] = Res[(int64_t)min(rbase + mfma32_row(r, lh), p.M - 1) * p.ldres + colc];
@@ -525,7 +556,7 @@ __device__ __forceinline__ void gemm_persistent(const Locator& loc, const int nt
         for (int r = 0; r < 16; ++r) {
           float v = acc[mi][ni][r] + bv;
           v = gemm_act(v, p.relu);
-          if (Res) v += rv[r];
+          if (EPI == 2 || Res) v += rv[r];
           if (p.relu_after) v = fmaxf(v, 0.f);
           ov[r] = v;
         }
@@ -545,6 +576,7 @@ __device__ __forceinline__ void gemm_persistent(const Locator& loc, const int nt
       }
     }
     cur = nxt;
+    t += per;
   }
 }
 
@@ -600,6 +632,44 @@ void k_gemm_stencil(const GemmP p, const StencilP st, const int batch) {
   __shared__ __attribute__((aligned(16))) float smem[TileSmem<64, 64, A_ROW>::FLOATS];
   const StencilLocator loc{p, st, (p.M + 63) / 64, (p.N + 63) / 64};
   gemm_persistent<64, 64, 32, 32, A_ROW, false, StencilLocator, 1>(loc, loc.mt * loc.nt * batch, smem);
+}
+
+// The same with the stencil rows gathered by the loader (gemm_persistent's EPI 3): W is the mask
+// feature itself, and the 4 N_l x K row copies of pn_bilinear_stencil_rows_f32 are never made.
+__global__ __launch_bounds__(256, (TileWgs<64, 64, A_ROW, false>::min_waves))
+void k_gemm_stencil_gather(const GemmP p, const StencilP st, const int batch) {
+  __shared__ __attribute__((aligned(16))) float smem[TileSmem<64, 64, A_ROW>::FLOATS];
+  const StencilLocator loc{p, st, (p.M + 63) / 64, (p.N + 63) / 64};
+  gemm_persistent<64, 64, 32, 32, A_ROW, false, StencilLocator, 3>(loc, loc.mt * loc.nt * batch, smem);
+}
+
+// First bottleneck of a ResNet stage: projection shortcut and conv3 in ONE launch.  Every 64x64
+// output tile is contracted twice (gemm_persistent's two-phase mode): first the shortcut (A = the
+// block input read as a 1x1 convolution of any stride), whose acc + bias stays in 16 registers per
+// lane, then conv3 (A = the 3x3 convolution's output, row-major, described as a 1x1 stride-1
+// convolution of a 1 x M image) with today's epilogue (+ bias, + residual, ReLU).  Two separate
+// accumulation chains: each output is bit for bit what the two launches give, and the shortcut
+// map is neither written nor read back.  The 16 kept registers still fit the 96 of five
+// workgroups per CU without scratch (94 VGPRs).
+#define PN_GEMM_WGS_PROJ PN_GEMM_WGS64
+struct ProjLocator {
+  const GemmP& p;    // conv3: phase 1, output geometry
+  const GemmP& sc;   // projection shortcut: phase 0
+  int mt, nt;
+  __device__ __forceinline__ const GemmP& P(int phase) const { return phase ? p : sc; }
+  __device__ __forceinline__ TileRef operator()(int T) const {
+    const int per_b = mt * nt;
+    const int bz = T / per_b, r = T - bz * per_b;
+    const int tm = r / nt;
+    return TileRef{0, bz, tm, r - tm * nt};
+  }
+};
+
+__global__ __launch_bounds__(256, PN_GEMM_WGS_PROJ)
+void k_gemm_proj(const GemmP p, const GemmP sc, const int batch) {
+  __shared__ __attribute__((aligned(16))) float smem[TileSmem<64, 64, A_CONV>::FLOATS];
+  const ProjLocator loc{p, sc, (p.M + 63) / 64, (p.N + 63) / 64};
+  gemm_persistent<64, 64, 32, 32, A_CONV, false, ProjLocator, 2>(loc, loc.mt * loc.nt * batch, smem);
 }
 
 // Several independent row-major GEMMs in ONE launch: the 64x64 tiles of all
@@ -1012,11 +1082,10 @@ extern "C" int pn_gemm_group_f32(const pn_gemm_desc* d, int count, void* stream)
   return PN_LAUNCH_CHECK();
 }
 
-extern "C" int pn_conv2d_nhwc_ex_f32(const float* in, const float* Wp, const float* bias,
-                                     const float* res, float* out, int B, int H, int W,
-                                     int Cin, int Cout, int KH, int KW, int stride, int pad,
-                                     int flags, float* splitk_scratch,
-                                     int64_t splitk_scratch_floats, void* stream) {
+// The implicit-GEMM descriptor of a channel-last convolution (argument checks included).
+static int fill_conv_params(const float* in, const float* Wp, const float* bias, const float* res,
+                            float* out, int B, int H, int W, int Cin, int Cout, int KH, int KW,
+                            int stride, int pad, int flags, GemmP* outp) {
   if (!in || !Wp || !out || B <= 0 || H <= 0 || W <= 0 || stride <= 0 || pad < 0)
     return PN_BAD_ARG;
   if (Cin % 32 || !aligned16(in) || !aligned16(Wp)) return PN_BAD_ARG;
@@ -1033,6 +1102,19 @@ extern "C" int pn_conv2d_nhwc_ex_f32(const float* in, const float* Wp, const flo
   p.relu_after = (flags & PN_GEMM_RELU_AFTER_RES) ? 1 : 0;
   p.aadd_rows = 1;
   p.H = H; p.Wd = W; p.Cin = Cin; p.KW = KW; p.pad = pad; p.stride = stride; p.Wo = Wo;
+  *outp = p;
+  return 0;
+}
+
+extern "C" int pn_conv2d_nhwc_ex_f32(const float* in, const float* Wp, const float* bias,
+                                     const float* res, float* out, int B, int H, int W,
+                                     int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                     int flags, float* splitk_scratch,
+                                     int64_t splitk_scratch_floats, void* stream) {
+  GemmP p;
+  if (int rc = fill_conv_params(in, Wp, bias, res, out, B, H, W, Cin, Cout, KH, KW, stride, pad,
+                                flags, &p))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
   // 64x64 tiles everywhere (3x3 FPN conv on MI355X: 625 us / 126 TFLOP/s, against 730
   // with 128x64 and 845 with 128x128 tiles, tools/gemm_probe.hip); the larger tiles stay
@@ -1050,6 +1132,82 @@ extern "C" int pn_conv2d_nhwc_f32(const float* in, const float* Wp, const float*
   return pn_conv2d_nhwc_ex_f32(in, Wp, bias, nullptr, out, B, H, W, Cin, Cout, KH, KW, 1, pad,
                                (flags & ~PN_GEMM_RELU) | (relu ? PN_GEMM_RELU : 0), nullptr, 0,
                                stream);
+}
+
+// Does pn_gemm_f32 contract `d` with the unsplit tile kernel (one fmaf chain over k per output)?
+static bool gemm_single_chain(const pn_gemm_desc* d) {
+  GemmP p;
+  if (pn_fill_params(d, &p) || gemm_use_skinny(d)) return false;
+  int cps;
+  return splitk_factor(p, d->batch, d->splitk_scratch, d->splitk_scratch_floats, &cps, d->flags) <= 1;
+}
+
+extern "C" int pn_bottleneck_proj_f32(const float* x, const float* Wsc, const float* bsc,
+                                      const float* t2, const float* W3, const float* b3,
+                                      float* idt, float* out, int B, int H, int W, int Cin,
+                                      int planes, int Cout, int stride, int flags,
+                                      float* splitk_scratch, int64_t splitk_scratch_floats,
+                                      void* stream) {
+  if (!x || !Wsc || !t2 || !W3 || !out || B <= 0 || H <= 0 || W <= 0 || stride <= 0 ||
+      Cin <= 0 || planes <= 0 || Cout <= 0)
+    return PN_BAD_ARG;
+  if (Cin % 32 || planes % 32 || !aligned16(x) || !aligned16(Wsc) || !aligned16(t2) || !aligned16(W3))
+    return PN_BAD_ARG;
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  const int64_t M = (int64_t)Ho * Wo;
+  const int64_t lim = (int64_t)1 << 29;
+  if (M * planes >= lim || M * B >= lim || (int64_t)Cout * Cin >= lim || (int64_t)Cout * planes >= lim)
+    return PN_BAD_ARG;
+  flags &= (0x3ff << PN_GEMM_RESERVE_SHIFT) | PN_GEMM_KSPLIT(31);
+  // the two launches this one replaces, as backbone.py issues them: the shortcut as a row-major
+  // GEMM over all B * H * W pixels (stride 1) or a strided 1x1 convolution, conv3 as a row-major
+  // GEMM with the shortcut as its residual
+  pn_gemm_desc d3{};
+  d3.A = t2; d3.lda = planes; d3.W = W3; d3.ldw = planes; d3.bias = b3;
+  d3.Res = idt; d3.ldres = Cout; d3.C = out; d3.ldc = Cout;
+  d3.M = (int)(M * B); d3.N = Cout; d3.K = planes; d3.batch = 1;
+  d3.flags = flags | PN_GEMM_RELU_AFTER_RES;
+  d3.splitk_scratch = splitk_scratch; d3.splitk_scratch_floats = splitk_scratch_floats;
+  pn_gemm_desc ds = d3;
+  ds.A = x; ds.lda = Cin; ds.W = Wsc; ds.ldw = Cin; ds.bias = bsc;
+  ds.Res = nullptr; ds.ldres = 0; ds.C = idt ? idt : out; ds.K = Cin; ds.flags = flags;
+  GemmP psc;
+  if (int rc = fill_conv_params(x, Wsc, bsc, nullptr, out, B, H, W, Cin, Cout, 1, 1, stride, 0,
+                                flags, &psc))
+    return rc;
+  // conv3's rows as a 1x1 stride-1 convolution of a 1 x M image per batch entry
+  GemmP p3;
+  if (int rc = fill_conv_params(t2, W3, b3, nullptr, out, B, 1, (int)M, planes, Cout, 1, 1, 1, 0,
+                                flags | PN_GEMM_RELU_AFTER_RES, &p3))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  // One launch only where all three contractions are single fmaf chains (no split-K, no skinny
+  // kernel): then every output is bit for bit the two launches'.  Otherwise: the two launches.
+  int cps;
+  bool fused = gemm_single_chain(&d3);
+  if (stride == 1) fused = fused && gemm_single_chain(&ds);
+  else fused = fused && splitk_factor(psc, B, splitk_scratch, splitk_scratch_floats, &cps, flags) <= 1;
+  if (fused) {
+    GemmP both = p3;
+    both.K = Cin + planes;
+    fused = splitk_factor(both, B, splitk_scratch, splitk_scratch_floats, &cps, flags) <= 1;
+  }
+  if (!fused) {
+    if (!idt) return PN_BAD_ARG;
+    if (stride == 1) {
+      if (int rc = pn_gemm_f32(&ds, stream)) return rc;
+    } else if (int rc = pn_conv2d_nhwc_ex_f32(x, Wsc, bsc, nullptr, idt, B, H, W, Cin, Cout, 1, 1,
+                                              stride, 0, flags, splitk_scratch,
+                                              splitk_scratch_floats, stream)) {
+      return rc;
+    }
+    return pn_gemm_f32(&d3, stream);
+  }
+  const int64_t ntiles = (int64_t)pn_cdiv((int)M, 64) * pn_cdiv(Cout, 64) * B;
+  static const int wgs = resident_wgs(k_gemm_proj, PN_GEMM_WGS_PROJ, 256);
+  hipLaunchKernelGGL(k_gemm_proj, dim3(persistent_grid(ntiles, wgs, flags)), dim3(256), 0, s, p3,
+                     psc, B);
+  return PN_LAUNCH_CHECK();
 }
 
 extern "C" int pn_mask_stencil_gemm_f32(const float* me, int64_t ld_me, int64_t stride_me,
@@ -1075,6 +1233,33 @@ extern "C" int pn_mask_stencil_gemm_f32(const float* me, int64_t ld_me, int64_t 
   const int64_t ntiles = (int64_t)pn_cdiv(Q, 64) * (p.N / 64) * B;
   static const int wgs = resident_wgs(k_gemm_stencil, TileWgs<64, 64, A_ROW, false>::value, 256);
   hipLaunchKernelGGL(k_gemm_stencil, dim3(persistent_grid(ntiles, wgs, flags)), dim3(256), 0, s, p, st, B);
+  return PN_LAUNCH_CHECK();
+}
+
+extern "C" int pn_mask_stencil_gather_gemm_f32(const float* me, int64_t ld_me, int64_t stride_me,
+                                               const float* mf, int64_t ld_mf, int64_t stride_mf,
+                                               uint32_t* bits, int32_t* rowall, int B, int Q,
+                                               int Nk, int K, int hi, int wi, int ho, int wo,
+                                               int flags, void* stream) {
+  if (!me || !mf || !bits || !rowall || B <= 0 || Q <= 0 || Nk <= 0 || K <= 0 || K % 32)
+    return PN_BAD_ARG;
+  if (hi <= 0 || wi <= 0 || ho <= 0 || wo <= 0 || (int64_t)ho * wo != Nk) return PN_BAD_ARG;
+  if (ld_me % 4 || ld_mf % 4 || stride_me % 4 || stride_mf % 4 || !aligned16(me) || !aligned16(mf))
+    return PN_BAD_ARG;
+  const int64_t lim = (int64_t)1 << 29;
+  if ((int64_t)(Q - 1) * ld_me + K >= lim || ((int64_t)hi * wi - 1) * ld_mf + K >= lim)
+    return PN_BAD_ARG;
+  GemmP p{};
+  p.A = me; p.W = mf; p.lda = ld_me; p.ldw = ld_mf; p.sA = stride_me; p.sW = stride_mf;
+  p.M = Q; p.K = K; p.aadd_rows = 1;
+  p.N = pn_cdiv(Nk, 16) * 64;            // 16 keys x 4 taps per 64-column tile
+  const StencilP st{bits, rowall, Nk, hi, wi, ho, wo};
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_fill_i32, dim3(pn_cdiv(B * Q, 256)), dim3(256), 0, s, rowall, 1, B * Q);
+  const int64_t ntiles = (int64_t)pn_cdiv(Q, 64) * (p.N / 64) * B;
+  static const int wgs = resident_wgs(k_gemm_stencil_gather, TileWgs<64, 64, A_ROW, false>::value, 256);
+  hipLaunchKernelGGL(k_gemm_stencil_gather, dim3(persistent_grid(ntiles, wgs, flags)), dim3(256), 0,
+                     s, p, st, B);
   return PN_LAUNCH_CHECK();
 }
 

@@ -148,6 +148,111 @@ extern "C" int pn_groupnorm_nhwc_f32(const float* x, const float* gamma, const f
   return PN_LAUNCH_CHECK();
 }
 
+// k_gn_apply (no ReLU) + the accumulate pass of k_bilinear_nhwc (resize.hip) in one pass over
+// the map: y = GN(x) + bilinear-up(coarse), the FPN's top-down add.  The same operations in the
+// same order as the two kernels -- the normalised value is rounded to fp32 exactly as k_gn_apply
+// stores it, the sample exactly as k_bilinear_nhwc forms it, then one add -- so the result is bit
+// for bit theirs; the two values pass through empty asm statements so that the compiler cannot
+// contract anything across the add that the two-kernel form could not.
+#define GN_UP_CH 4   // pixels per thread whose loads are in flight together
+__global__ __launch_bounds__(64 * GN_SUB) void k_gn_apply_up(
+    const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float* __restrict__ y, const double* __restrict__ partials, const float* __restrict__ coarse,
+    int64_t HW, int Wf, int hc, int wc, int Hf, int G, float eps, int64_t xbs, int64_t ybs,
+    int64_t cbs) {
+  __shared__ double acc[GN_SUB][64];
+  __shared__ float stat[64][2];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const int nblk = gridDim.x;
+  {  // reduce partials of image b (k_gn_apply's order)
+    const int col = tid & 63, part = tid >> 6;
+    double t = 0.0;
+    if (col < 2 * G)
+      for (int i = part; i < nblk; i += GN_SUB)
+        t += partials[((int64_t)b * nblk + i) * G * 2 + col];
+    acc[part][col] = t;
+  }
+  __syncthreads();
+  if (tid < G) {
+    const double n = (double)HW * (256 / G);
+    double s = 0.0, ss = 0.0;
+    for (int k = 0; k < GN_SUB; ++k) {
+      s += acc[k][2 * tid];
+      ss += acc[k][2 * tid + 1];
+    }
+    const double mean = s / n;
+    double var = ss / n - mean * mean;
+    if (var < 0.0) var = 0.0;
+    stat[tid][0] = (float)mean;
+    stat[tid][1] = (float)(1.0 / sqrt(var + (double)eps));
+  }
+  __syncthreads();
+  const int c4 = tid & 63, sub = tid >> 6;
+  const int g = (c4 * 4) / (256 / G);
+  const float mean = stat[g][0], rstd = stat[g][1];
+  const float4 gg = ld4(gamma + c4 * 4), bb = ld4(beta + c4 * 4);
+  const int64_t p0 = (int64_t)blockIdx.x * GN_PIX;
+  const float* xb = x + (int64_t)b * xbs;
+  float* yb = y + (int64_t)b * ybs;
+  const float* ib = coarse + (int64_t)b * cbs + c4 * 4;
+  const int64_t rs = (int64_t)wc * 256, cs = 256;
+  constexpr int NP = GN_PIX / GN_SUB;
+#pragma unroll
+  for (int j0 = 0; j0 < NP; j0 += GN_UP_CH) {
+    float4 v[GN_UP_CH], v00[GN_UP_CH], v01[GN_UP_CH], v10[GN_UP_CH], v11[GN_UP_CH];
+    Tap tys[GN_UP_CH], txs[GN_UP_CH];
+#pragma unroll
+    for (int j = 0; j < GN_UP_CH; ++j) {   // all loads first, unconditional (clamped)
+      const int pix = (int)min(p0 + sub + (j0 + j) * GN_SUB, HW - 1);
+      const int oy = pix / Wf, ox = pix - oy * Wf;
+      const Tap ty = make_tap(oy, hc, Hf), tx = make_tap(ox, wc, Wf);
+      tys[j] = ty; txs[j] = tx;
+      v[j] = ld4(xb + (int64_t)pix * 256 + c4 * 4);
+      v00[j] = ld4(ib + ty.i0 * rs + tx.i0 * cs); v01[j] = ld4(ib + ty.i0 * rs + tx.i1 * cs);
+      v10[j] = ld4(ib + ty.i1 * rs + tx.i0 * cs); v11[j] = ld4(ib + ty.i1 * rs + tx.i1 * cs);
+    }
+#pragma unroll
+    for (int j = 0; j < GN_UP_CH; ++j) {
+      const int64_t pix = p0 + sub + (j0 + j) * GN_SUB;
+      const Tap ty = tys[j], tx = txs[j];
+      // Written out as the fmaf chains the two kernels compile to (which product of a sum the
+      // compiler folds into the fma decides the rounding): GN = fma(gamma, (x - mean) rstd, beta);
+      // sample: top = fma(l1x, v01, l0x v00), bottom = fma(l0x, v10, l1x v11),
+      // r = fma(l0y, top, l1y bottom).  The test compares against the pair bit for bit.
+#define GN_O(c) fmaf((v[j].c - mean) * rstd, gg.c, bb.c)
+#define UP_R(c) fmaf(ty.l0, fmaf(tx.l1, v01[j].c, tx.l0 * v00[j].c), \
+                     ty.l1 * fmaf(tx.l0, v10[j].c, tx.l1 * v11[j].c))
+      float4 o = make_float4(GN_O(x), GN_O(y), GN_O(z), GN_O(w));
+      float4 r = make_float4(UP_R(x), UP_R(y), UP_R(z), UP_R(w));
+#undef GN_O
+#undef UP_R
+      asm volatile("" : "+v"(o.x), "+v"(o.y), "+v"(o.z), "+v"(o.w));
+      asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w));
+      if (pix < HW) st4(yb + pix * 256 + c4 * 4, add4(o, r));
+    }
+  }
+}
+
+extern "C" int pn_groupnorm_upadd_nhwc_f32(const float* x, const float* gamma, const float* beta,
+                                           float* y, double* partials, const float* coarse, int B,
+                                           int H, int W, int hc, int wc, int C, int G, float eps,
+                                           int64_t x_bstride, int64_t y_bstride,
+                                           int64_t coarse_bstride, void* stream) {
+  if (!x || !gamma || !beta || !y || !partials || !coarse) return PN_BAD_ARG;
+  if (C != 256 || G <= 0 || G > 32 || 256 % G || (256 / G) % 4 || B <= 0 || B > 65535 || H <= 0 ||
+      W <= 0 || hc <= 0 || wc <= 0)
+    return PN_BAD_ARG;
+  if ((x_bstride | y_bstride | coarse_bstride) & 3) return PN_BAD_ARG;
+  const int64_t HW = (int64_t)H * W;
+  if (HW >= ((int64_t)1 << 31)) return PN_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(pn_groupnorm_nblk(HW), B);
+  hipLaunchKernelGGL(k_gn_partial, grid, dim3(64 * GN_SUB), 0, s, x, partials, HW, G, x_bstride);
+  hipLaunchKernelGGL(k_gn_apply_up, grid, dim3(64 * GN_SUB), 0, s, x, gamma, beta, y, partials,
+                     coarse, HW, W, hc, wc, H, G, eps, x_bstride, y_bstride, coarse_bstride);
+  return PN_LAUNCH_CHECK();
+}
+
 __global__ __launch_bounds__(256) void k_l2norm256(const float* __restrict__ x,
                                                    float* __restrict__ y, int64_t rows,
                                                    float eps) {

@@ -147,6 +147,15 @@ class CrossHead2:
         # logits, blend, threshold and pack in the GEMM's epilogue (pn_mask_stencil_gemm_f32;
         # bit-identical to the GEMM -> pn_mask_pack_stencil pair, which False restores)
         self.fuse_mask_pack = True
+        # ... and that launch gathers its stencil rows from the mask feature itself
+        # (pn_mask_stencil_gather_gemm_f32): stage A no longer copies them into pl.MFs, three
+        # launches and 90 MB of writes per 800 x 1333 image; bit-identical, False restores the copies
+        self.gather_mask_stencil = True
+        # lateral GroupNorm and the top-down upsample-add as one pass over the stride-4 map
+        # (pn_groupnorm_upadd_nhwc_f32) instead of two, bit-identical.  Off by default: 78 against
+        # 90 us stand-alone, but no difference in the pipelined step beyond its run-to-run spread
+        # (labnotes R7.3)
+        self.fuse_lateral_upadd = False
         # encoder sites whose Linear + identity + LayerNorm run as one row-owning launch
         # (pn_linear_res_ln_f32): "proj" = output_proj -> norms.0, "ffn" = FFN-2 -> norms.1;
         # () = the GEMM -> LayerNorm pairs of rounds 1-3 (bit-identical either way)
@@ -702,12 +711,18 @@ class CrossHead2:
         hip.gemm(f, w[pd + "lateral_convs.0.conv.weight"], pl.T1, M=HW2, N=256, K=cin,
                  lda=cin if pl.nhwc else HW2, ldw=cin, ldc=256, batch=B, sA=cin * HW2,
                  sC=HW2 * 256, colmajor=not pl.nhwc)
-        hip.groupnorm_nhwc(pl.T1, w[pd + "lateral_convs.0.gn.weight"],
-                           w[pd + "lateral_convs.0.gn.bias"], pl.T2, pl.gn_part, B, HW2,
-                           self.gn_groups, False, HW2 * 256, HW2 * 256)
         h2, w2 = pl.shapes[2]
-        hip.bilinear_nhwc(pl.X[:, pl.start[2]:], pl.T2, B, h2, w2, H2, W2, 256, True, SN * 256,
-                          HW2 * 256)
+        if getattr(self, "fuse_lateral_upadd", False):
+            hip.groupnorm_upadd_nhwc(pl.T1, w[pd + "lateral_convs.0.gn.weight"],
+                                     w[pd + "lateral_convs.0.gn.bias"], pl.T2, pl.gn_part,
+                                     pl.X[:, pl.start[2]:], B, H2, W2, h2, w2, self.gn_groups,
+                                     HW2 * 256, HW2 * 256, SN * 256)
+        else:
+            hip.groupnorm_nhwc(pl.T1, w[pd + "lateral_convs.0.gn.weight"],
+                               w[pd + "lateral_convs.0.gn.bias"], pl.T2, pl.gn_part, B, HW2,
+                               self.gn_groups, False, HW2 * 256, HW2 * 256)
+            hip.bilinear_nhwc(pl.X[:, pl.start[2]:], pl.T2, B, h2, w2, H2, W2, 256, True, SN * 256,
+                              HW2 * 256)
         if self.conv_algo == "winograd4":
             hip.conv3x3_winograd43(pl.T2, w[pd + "output_convs.0.conv.winograd4"], None, pl.T1,
                                    pl.wV, pl.wM, B, H2, W2, 256, 256, False)
@@ -726,11 +741,15 @@ class CrossHead2:
             for l, (h, wd) in enumerate(pl.shapes):
                 hip.bilinear_nhwc(pl.MF, pl.MFd[l], B, H2, W2, h, wd, 256, False, HW2 * 256,
                                   pl.N[l] * 256)
-        elif self.exact_mask_order != "full":
+        elif self.exact_mask_order != "full" and not self._gathers_stencil():
             # the mask-feature rows each level's bilinear stencils read, once per image
             for l, (h, wd) in enumerate(pl.shapes):
                 hip.bilinear_stencil_rows(pl.MF, pl.MFs[l], B, H2, W2, h, wd, 256, HW2 * 256,
                                           4 * pl.N[l] * 256)
+
+    def _gathers_stencil(self):
+        return bool(self.exact_mask_order and self.exact_mask_order != "full" and
+                    self.fuse_mask_pack and getattr(self, "gather_mask_stencil", True))
 
     def _encoder_fp32(self, pl):
         """The six encoder layers on the exact-fp32 MFMA kernels (rounds 1-5)."""
@@ -857,8 +876,12 @@ class CrossHead2:
         elif self.exact_mask_order and self.fuse_mask_pack:
             # logits, blend, threshold and pack in ONE launch: the same products in the same
             # order as the pair below (bit-identical bits), without the Q x 4 N_l logit map
-            hip.mask_stencil_gemm(pl.me if me is None else me, pl.MFs[lvl], pl.bits, pl.rowall,
-                                  B, Q, pl.hw2[0], pl.hw2[1], h, wd)
+            if self._gathers_stencil():
+                hip.mask_stencil_gather_gemm(pl.me if me is None else me, pl.MF, pl.bits,
+                                             pl.rowall, B, Q, pl.hw2[0], pl.hw2[1], h, wd)
+            else:
+                hip.mask_stencil_gemm(pl.me if me is None else me, pl.MFs[lvl], pl.bits,
+                                      pl.rowall, B, Q, pl.hw2[0], pl.hw2[1], h, wd)
             return
         elif self.exact_mask_order:
             hip.gemm(pl.me if me is None else me, pl.MFs[lvl], pl.ML4, M=Q, N=4 * n, K=256,
@@ -1084,7 +1107,8 @@ class CrossHead2:
         every buffer is a view of the slot's arena (plans.py)."""
         cfg = (self.exact_mask_order, self.conv_algo, self.fuse_ppn_front, self.grid_reserve,
                tuple(self.enc_fused_ln), self.group_input_convs,
-               getattr(self, "fuse_mask_pack", True), self.gemm_arithmetic, self.msda_s3_out)
+               getattr(self, "fuse_mask_pack", True), self.gemm_arithmetic, self.msda_s3_out,
+               getattr(self, "gather_mask_stencil", True), getattr(self, "fuse_lateral_upadd", False))
         if pl.graph_cfg != cfg:          # a captured graph bakes these switches in
             pl.graph_a = pl.graph_b = None
             pl.graphs_a = OrderedDict()

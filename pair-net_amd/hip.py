@@ -64,6 +64,7 @@ _SIGS = {
     "pn_gemm_group_f32": (C.c_int, [C.POINTER(GemmDesc), C.c_int, _vp]),
     "pn_conv2d_nhwc_f32": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 10 + [_vp]),
     "pn_conv2d_nhwc_ex_f32": (C.c_int, [_vp] * 5 + [_i32] * 10 + [_vp, _i64, _vp]),
+    "pn_bottleneck_proj_f32": (C.c_int, [_vp] * 8 + [_i32] * 8 + [_vp, _i64, _vp]),
     "pn_stem7x7s2_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pn_maxpool3x3s2_nhwc_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pn_winograd_f23_input_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
@@ -81,6 +82,7 @@ _SIGS = {
     "pn_groupnorm_nblk": (C.c_int, [_i64]),
     "pn_groupnorm_nhwc_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32,
                                         _i32, _f32, _i32, _i64, _i64, _vp]),
+    "pn_groupnorm_upadd_nhwc_f32": (C.c_int, [_vp] * 6 + [_i32] * 7 + [_f32, _i64, _i64, _i64, _vp]),
     "pn_l2normalize_f32": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _vp]),
     "pn_ffn_scratch_floats": (_i64, [_i32, _i32]),
     "pn_ffn_ln_f32": (C.c_int, [_vp] * 9 + [_i32, _i32, _i32, _f32, _vp]),
@@ -148,6 +150,8 @@ _SIGS = {
     "pn_mask_pack_stencil": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "pn_mask_stencil_gemm_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp] +
                                  [_i32] * 9 + [_vp]),
+    "pn_mask_stencil_gather_gemm_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp] +
+                                        [_i32] * 9 + [_vp]),
     "pn_bilinear_stencil_rows_f32": (C.c_int, [_vp, _vp] + [_i32] * 6 + [_i64, _i64, _vp]),
     "pn_attn_scratch_floats": (_i64, [_i32, _i32, _i32]),
     "pn_attention_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
@@ -197,7 +201,7 @@ _SIGS = {
                                                 _i32, _vp]),
 }
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 29   # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
+ABI_VERSION = 30   # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
 
 _lib = None
 
@@ -468,6 +472,23 @@ def conv2d_ex(x, wp, bias, res, out, B, H, W, Cin, Cout, KH, KW, stride, pad, re
            "pn_conv2d_nhwc_ex_f32")
 
 
+def bottleneck_proj(x, wsc, bsc, t2, w3, b3, idt, out, B, H, W, Cin, planes, stride,
+                    scratch=None):
+    """out = relu(conv3(t2) + shortcut(x)) of a stage's first bottleneck in one launch
+    (pn_bottleneck_proj_f32); `idt` is the intermediate of the two-launch form the library
+    takes where its split-K / skinny rules apply."""
+    Cout = w3.shape[0]
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    flops = 2.0 * B * Ho * Wo * Cout * (Cin + planes)
+    nbytes = 4.0 * (B * (Ho * Wo * (Cin + planes + Cout)) + Cout * (Cin + planes))
+    _check(_launch("k_gemm_proj", flops, nbytes,
+                   lambda: lib().pn_bottleneck_proj_f32(
+                       _ptr(x), _ptr(wsc), _ptr(bsc), _ptr(t2), _ptr(w3), _ptr(b3), _ptr(idt),
+                       _ptr(out), B, H, W, Cin, planes, Cout, stride, _reserve_flag(),
+                       _ptr(scratch), scratch.numel() if scratch is not None else 0, _stream())),
+           "pn_bottleneck_proj_f32")
+
+
 def stem7x7s2(img, wp, bias, out, B, H, W):
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     _check(_launch("k_stem7x7s2", 2.0 * B * Ho * Wo * 64 * 147,
@@ -713,6 +734,15 @@ def groupnorm_nhwc(x, gamma, beta, out, partials, B, HW, G, relu, x_bstride, y_b
         256, G, eps, int(relu), x_bstride, y_bstride, _stream()), "pn_groupnorm_nhwc_f32")
 
 
+def groupnorm_upadd_nhwc(x, gamma, beta, out, partials, coarse, B, H, W, hc, wc, G, x_bstride,
+                         y_bstride, coarse_bstride, eps=1e-5):
+    """out = GroupNorm(x) + bilinear-up(coarse) in one pass (pn_groupnorm_upadd_nhwc_f32)."""
+    _check(lib().pn_groupnorm_upadd_nhwc_f32(
+        _ptr(x), _ptr(gamma), _ptr(beta), _ptr(out), _ptr(partials, torch.float64), _ptr(coarse),
+        B, H, W, hc, wc, 256, G, eps, x_bstride, y_bstride, coarse_bstride, _stream()),
+        "pn_groupnorm_upadd_nhwc_f32")
+
+
 def ffn_scratch_floats(M, hidden):
     return lib().pn_ffn_scratch_floats(M, hidden)
 
@@ -824,6 +854,20 @@ def mask_stencil_gemm(me, rows, bits, rowall, B, Q, hi, wi, ho, wo, K=256):
                        _ptr(bits, torch.int32), _ptr(rowall, torch.int32), B, Q, Nk, K, hi, wi,
                        ho, wo, _reserve_flag(), _stream()),
                    meta=(Q, 4 * Nk, K, B, False)), "pn_mask_stencil_gemm_f32")
+
+
+def mask_stencil_gather_gemm(me, mf, bits, rowall, B, Q, hi, wi, ho, wo, K=256):
+    """mask_stencil_gemm reading the stencil rows in place from the mask feature `mf`
+    [B, hi*wi, K] (csrc/gemm.hip k_gemm_stencil_gather)."""
+    Nk = ho * wo
+    _check(_launch("k_gemm_stencil_gather", 2.0 * B * Q * 4 * Nk * K,
+                   4.0 * B * (Q * K + 4 * Nk * K) + B * Q * Nk / 8.0,
+                   lambda: lib().pn_mask_stencil_gather_gemm_f32(
+                       _ptr(me), me.stride(0), Q * me.stride(0), _ptr(mf), mf.stride(-2),
+                       mf.stride(0) if mf.dim() == 3 else hi * wi * mf.stride(-2),
+                       _ptr(bits, torch.int32), _ptr(rowall, torch.int32), B, Q, Nk, K, hi, wi,
+                       ho, wo, _reserve_flag(), _stream()),
+                   meta=(Q, 4 * Nk, K, B, False)), "pn_mask_stencil_gather_gemm_f32")
 
 
 def bilinear_stencil_rows(x, out, B, hi, wi, ho, wo, Cc, in_bstride, out_bstride):
