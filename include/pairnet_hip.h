@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PN_ABI_VERSION 30
+#define PN_ABI_VERSION 31
 int pn_abi_version(void);
 
 /* ------------------------------------------------------------------------- *
@@ -891,6 +891,23 @@ int pn_window_attention_bwd_f32(const float* qkv, int64_t ldqkv, const float* qk
                                 int shift, float scale, void* stream);
 /* out[ci][T-1-t][co] = in[co][t][ci]: a "same" convolution's weight as its data gradient reads it */
 int pn_conv_weight_bwd_layout_f32(const float* in, float* out, int Co, int T, int Ci, void* stream);
+/* Training-mode dropout of the Relation Fusion decoder's FFN (csrc/dropout.hip): mmcv FFN.layers'
+ * two nn.Dropout(ffn_drop) -- after the ReLU on the hidden rows and on the FFN's output before the
+ * identity shortcut -- under configs/mask2former/pairnet.py:121-129 (relation_decoder ffn_cfgs
+ * ffn_drop=0.1; every other rate of that file is 0.0).  Stateless: the keep bit of element i is
+ * word i % 4 of Philox4x32-10 at counter (i / 4, subseq, site, step), key (seed & 0xffffffff,
+ * seed >> 32), kept <=> word >= (uint32)((double)p * 2^32); no mask is stored, the backward pass is
+ * the same call on the gradient.  With s = (float)(1 / (1 - (double)p)):
+ *   y[i] = kept ? x[i] * s : 0            (res == NULL)
+ *   y[i] = kept ? fmaf(x[i], s, res[i]) : res[i]
+ * y may alias x.  x / res / y 16-byte aligned, 0 < n <= 2^34, 0 <= p < 1 (p == 0: y == x resp.
+ * x + res bitwise). */
+int pn_dropout_f32(const float* x, const float* res /* may be NULL */, float* y, int64_t n, float p,
+                   uint64_t seed, uint32_t subseq, uint32_t step, uint32_t site, void* stream);
+/* keep[i] = 1 where pn_dropout_f32 with the same (p, seed, subseq, step, site) keeps element i, else
+ * 0 (the mask made visible: tests, the float64 gradient oracle; same nn.Dropout call sites). */
+int pn_dropout_keep_u8(uint8_t* keep, int64_t n, float p, uint64_t seed, uint32_t subseq,
+                       uint32_t step, uint32_t site, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * The optimizer step (csrc/optim.hip) over one flat fp32 parameter buffer: what mmcv's

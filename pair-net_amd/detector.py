@@ -545,7 +545,8 @@ class PSGTr:
         and norm as configs/mask2former/pairnet_swinb.py does (`frozen_stages=3`,
         `SwinBackboneGrad`); False freezes either.  Other keywords go to TailTrainer (lr, lr_mult,
         group, drop_path, train_decoder=False / train_pixel_decoder=False for the frozen-detector
-        regimes)."""
+        regimes; `dropout=True` trains with the relation decoder's configured FFN dropout,
+        `seed=` its masks -- nothing of it lives here, the keywords pass through)."""
         from .backbone import ResNet50Hip
         from .train import TailTrainer
         if type(self.bbox_head) is not CrossHead2:
@@ -576,7 +577,9 @@ class PSGTr:
           name contains "loss" (`_parse_losses`).
 
         Ground-truth masks at image size are prepared like the reference's (pad to the batch
-        tensor, nearest half-size), then `trainer().step` runs."""
+        tensor, nearest half-size), then `trainer().step` runs -- the trainer built by an earlier
+        `trainer(...)` call if there is one (e.g. `trainer(dropout=True)` for the reference's
+        train-mode FFN dropout), else the default, deterministic one."""
         mmdet_form = isinstance(img, dict)
         if mmdet_form:
             data = img

@@ -26,13 +26,41 @@ Checked against autograd through the reference-pinned oracle (tests/test_grad_gp
 relative on `reldec.npz`, `ppn_sep.npz` and the queries of an 800x1333 image).
 """
 import math
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 
 from . import hip
 
-__all__ = ["RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad"]
+__all__ = ["RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad",
+           "FfnDropout"]
+
+
+class FfnDropout(namedtuple("FfnDropout", "p seed subseq step layer")):
+    """Descriptor of the Relation Fusion decoder's training-mode FFN dropout (mmcv FFN.layers: two
+    `nn.Dropout(ffn_drop)` per layer; configs/mask2former/pairnet.py:121-129): rate `p`, and the
+    counter the keep bits are a function of (csrc/dropout.hip) -- `seed`, `subseq` (the
+    data-parallel rank), `step` (the iteration), `layer` (filled in per layer by the tape).  Site
+    2 * layer + 0 is the hidden rows [B * R, ffn] after the ReLU, 2 * layer + 1 the FFN's output
+    [B * R, 256] before the shortcut; the element index is the position in the contiguous
+    batch-major buffer.  The backward pass passes the same descriptor: nothing is stored."""
+    __slots__ = ()
+
+    def __new__(cls, p, seed=0, subseq=0, step=0, layer=0):
+        p = float(p)
+        if not 0.0 <= p < 1.0:
+            raise ValueError("dropout rate %r outside [0, 1)" % p)
+        return super().__new__(cls, p, int(seed), int(subseq), int(step), int(layer))
+
+    def apply(self, x, out, which, res=None):
+        """out = drop(x) (+ res) at this layer's site `which` (0: hidden rows, 1: FFN output)."""
+        hip.dropout(x, out, self.p, self.seed, self.subseq, self.step, 2 * self.layer + which,
+                    res=res)
+
+    def keep(self, n, which, device=None):
+        """The site's keep bits for n elements (uint8 device tensor; for tests and oracles)."""
+        return hip.dropout_keep(n, self.p, self.seed, self.subseq, self.step,
+                                2 * self.layer + which, device=device)
 
 
 class RelationTailGrad:
@@ -186,7 +214,10 @@ class RelationTailGrad:
     # ------------------------------------------------------------------ forward with a tape
     @torch.no_grad()
     @hip.on_device
-    def forward(self, q, sub_pos=None, obj_pos=None):
+    def forward(self, q, sub_pos=None, obj_pos=None, dropout=None):
+        """`dropout` (an `FfnDropout`, default None): run the Relation Fusion decoder in the
+        reference's train mode; nothing else of the tail has a non-zero rate.  `self.t["rel"]` keeps
+        the returned relation logits."""
         head, w, E = self.head, self.head.w, self._E
         Q, R = self.Q, self.R
         if not (q.is_cuda and q.dtype == torch.float32 and q.dim() == 2 and q.shape[1] == 256
@@ -231,23 +262,26 @@ class RelationTailGrad:
         # ---- pair features (:342-351) ----
         pair = E(B * 2 * R, 256)
         hip.gather_rows(q, pair_idx, pair, B, Q, 2 * R, 256)
-        rel = self._relation_forward(pair, B)
+        rel = self._relation_forward(pair, B, dropout)
         sub, obj = E(B, R, nc), E(B, R, nc)
         hip.gather_rows(cls, sub_pos, sub, B, Q, R, nc)
         hip.gather_rows(cls, obj_pos, obj, B, Q, R, nc)
         return dict(rel=rel, importance=imp, importance_raw=raw, sub=sub, obj=obj, cls=cls,
                     sub_pos=sub_pos, obj_pos=obj_pos)
 
-    def _layer_fwd(self, pre, x, qpos, K, V, B, nq, nk, ffn, scr, bits=None, rowall=None):
+    def _layer_fwd(self, pre, x, qpos, K, V, B, nq, nk, ffn, scr, bits=None, rowall=None,
+                   drop=None):
         """One post-norm decoder layer (facebook_detr.py:378-432; order cross-attention, norm,
         self-attention, norm, FFN, norm) over given key / value projections K, V (2-D views
-        [B * nk, 256], free row strides) with every intermediate kept; returns (tape, output)."""
+        [B * nk, 256], free row strides) with every intermediate kept; returns (tape, output).
+        `drop` (an `FfnDropout` carrying this layer's index, or None): the FFN's two training-mode
+        dropouts; the tape then keeps the DROPPED, scaled hidden rows in s["h"]."""
         w, E = self.head.w, self._E
         M = B * nq
         ac, as_ = pre + "attentions.0.attn.", pre + "attentions.1.attn."
         Wc, bc = w[ac + "in_proj_weight"], w[ac + "in_proj_bias"]
         Ws, bs = w[as_ + "in_proj_weight"], w[as_ + "in_proj_bias"]
-        s = dict(x_in=x, K=K, V=V, bits=bits, rowall=rowall)
+        s = dict(x_in=x, K=K, V=V, bits=bits, rowall=rowall, drop=drop)
         # cross-attention
         s["xp"] = E(M, 256)
         hip.add_periodic(x, qpos, s["xp"])
@@ -279,8 +313,14 @@ class RelationTailGrad:
         hip.linear(s["x2"], w[pre + "ffns.0.layers.0.0.weight"],
                    w[pre + "ffns.0.layers.0.0.bias"], s["h"], relu=True)
         s["y3"] = E(M, 256)
-        hip.linear(s["h"], w[pre + "ffns.0.layers.1.weight"], w[pre + "ffns.0.layers.1.bias"],
-                   s["y3"], res=s["x2"])
+        if drop is None:
+            hip.linear(s["h"], w[pre + "ffns.0.layers.1.weight"], w[pre + "ffns.0.layers.1.bias"],
+                       s["y3"], res=s["x2"])
+        else:
+            drop.apply(s["h"], s["h"], 0)       # what layers.1 consumes and its d W contracts with
+            hip.linear(s["h"], w[pre + "ffns.0.layers.1.weight"], w[pre + "ffns.0.layers.1.bias"],
+                       s["y3"])
+            drop.apply(s["y3"], s["y3"], 1, res=s["x2"])          # y3 = x2 + drop(layers.1 out)
         out = E(M, 256)
         hip.layernorm(s["y3"], w[pre + "norms.2.weight"], w[pre + "norms.2.bias"], out)
         return s, out
@@ -294,9 +334,18 @@ class RelationTailGrad:
         Wc, Ws = w[ac + "in_proj_weight"], w[as_ + "in_proj_weight"]
         # norm2 <- FFN
         dy3 = self._ln_bwd(dx, s["y3"], pre + "norms.2.", grads)
-        dh = self._lin_bwd(dy3, s["h"], w[pre + "ffns.0.layers.1.weight"], grads,
+        # dropout is linear: its backward is the same launch on the gradient (the forward's
+        # counter, kept in the tape); the shortcut's share of dy3 stays un-dropped
+        drop = s["drop"]
+        dz = dy3
+        if drop is not None:
+            dz = E(M, 256)
+            drop.apply(dy3, dz, 1)
+        dh = self._lin_bwd(dz, s["h"], w[pre + "ffns.0.layers.1.weight"], grads,
                            pre + "ffns.0.layers.1.weight", pre + "ffns.0.layers.1.bias")
-        hip.relu_bwd(dh, s["h"], dh)
+        if drop is not None:
+            drop.apply(dh, dh, 0)
+        hip.relu_bwd(dh, s["h"], dh)       # (saved h > 0 <=> kept and pre-activation > 0)
         dx2 = self._lin_bwd(dh, s["x2"], w[pre + "ffns.0.layers.0.0.weight"], grads,
                             pre + "ffns.0.layers.0.0.weight", pre + "ffns.0.layers.0.0.bias")
         self._acc(dx2, dy3)                                   # the FFN's identity shortcut
@@ -327,7 +376,7 @@ class RelationTailGrad:
         self._acc(dxp, dy1)                                   # identity shortcut
         return dxp, dK, dV
 
-    def _relation_forward(self, pair, B):
+    def _relation_forward(self, pair, B, dropout=None):
         """The six Relation Fusion layers over `pair` [B * 2R, 256] with every intermediate kept."""
         head, w, E = self.head, self.head.w, self._E
         R, t = self.R, self.t
@@ -348,13 +397,21 @@ class RelationTailGrad:
             hip.linear(pairp, Wc[256:512], bc[256:512], KV[:, :256])
             hip.linear(pair, Wc[512:], bc[512:], KV[:, 256:])
             s, x = self._layer_fwd(pre, x, rpos, KV[:, :256], KV[:, 256:], B, R, 2 * R, self.ffn,
-                                   scr)
+                                   scr, drop=self._drop_of(dropout, i))
             layers.append(s)
         t["layers"], t["r_out"] = layers, x
         C = w["rel_cls_embed.weight"].shape[0]
         rel = E(B, R, C)
         hip.linear(x, w["rel_cls_embed.weight"], w["rel_cls_embed.bias"], rel.view(M, C))
+        t["rel"] = rel
         return rel
+
+    @staticmethod
+    def _drop_of(dropout, layer):
+        """The descriptor of one layer, or None for no dropout (None, or rate 0: the plain layer's launches)."""
+        if dropout is None or dropout.p == 0.0:
+            return None
+        return dropout._replace(layer=layer)
 
     # ------------------------------------------------------------------ backward
     def _zero_grads(self):
@@ -399,12 +456,13 @@ class RelationTailGrad:
 
     @torch.no_grad()
     @hip.on_device
-    def relation_forward(self, pair):
+    def relation_forward(self, pair, dropout=None):
         """The Relation Fusion decoder alone: pair features [B * 2R, 256] (per image the R
-        subject rows, then the R object rows) -> relation logits [B, R, C], taped."""
+        subject rows, then the R object rows) -> relation logits [B, R, C], taped.  `dropout`:
+        an `FfnDropout` (the FFNs' training-mode dropout), default None."""
         B = pair.shape[0] // (2 * self.R)
         self.t = dict(B=B, q=None)
-        return self._relation_forward(pair.contiguous(), B)
+        return self._relation_forward(pair.contiguous(), B, dropout)
 
     @torch.no_grad()
     @hip.on_device
@@ -568,7 +626,9 @@ class HeadGrad(RelationTailGrad):
 
     @torch.no_grad()
     @hip.on_device
-    def forward_from_plan(self, pl, sub_pos=None, obj_pos=None):
+    def forward_from_plan(self, pl, sub_pos=None, obj_pos=None, dropout=None):
+        """`dropout` reaches the Relation Fusion decoder only: the nine masked layers' rate is 0.0
+        in the reference and their outputs feed the masks and the pair selection."""
         head, w, E = self.head, self.head.w, self._E
         B, Q = pl.B, self.Q
         full = head.exact_mask_order == "full"
@@ -592,7 +652,7 @@ class HeadGrad(RelationTailGrad):
             if i + 1 < head.num_dec_layers:      # post_norm + mask_embed -> the next layer's mask
                 head._head_embed(x, pl, False, full)
         self.dt = dict(layers=layers, pl=pl, q_out=x)
-        return self.forward(x, sub_pos, obj_pos)
+        return self.forward(x, sub_pos, obj_pos, dropout)
 
     @torch.no_grad()
     @hip.on_device

@@ -46,6 +46,24 @@ def _decoder_param_shapes(prefix, num_layers, ffn_dim, out):
     out[prefix + ".post_norm.bias"] = (256,)
 
 
+def _drop_rates(cfg, prefix=""):
+    """{dotted config key: rate} of every non-zero dropout setting below `cfg` (mmcv's spellings:
+    `ffn_drop`, `attn_drop`, `proj_drop`, MultiScaleDeformableAttention's `dropout`, and a
+    `dropout_layer=dict(type=..., drop_prob=)`)."""
+    out = OrderedDict()
+    items = cfg.items() if isinstance(cfg, dict) else enumerate(cfg)
+    for k, v in items:
+        key = "%s%s" % (prefix, k)
+        if k == "dropout_layer" and isinstance(v, dict):
+            v = v.get("drop_prob", 0.0)
+        if k in ("ffn_drop", "attn_drop", "proj_drop", "dropout", "dropout_layer"):
+            if isinstance(v, (int, float)) and float(v) != 0.0:
+                out[key] = float(v)
+        elif isinstance(v, (dict, list, tuple)):
+            out.update(_drop_rates(v, key + "."))
+    return out
+
+
 class CrossHead2:
     """Drop-in for the reference's `CrossHead2` (inference half)."""
 
@@ -107,6 +125,14 @@ class CrossHead2:
         self.dec_ffn = transformer_decoder.transformerlayers.ffn_cfgs.feedforward_channels
         self.num_rel_layers = relation_decoder.num_layers
         self.rel_ffn = relation_decoder.transformerlayers.ffn_cfgs.feedforward_channels
+        # the one non-zero dropout rate of the reference's config (pairnet.py:126): the training
+        # step honours it on request (train.py `dropout=`); inference never drops.  Every OTHER
+        # configured rate is recorded by its key so that the trainer can refuse what it cannot do.
+        self.rel_ffn_drop = float(relation_decoder.transformerlayers.ffn_cfgs.get("ffn_drop", 0.0))
+        self.other_drop_rates = _drop_rates(dict(pixel_decoder=pixel_decoder,
+                                                 transformer_decoder=transformer_decoder,
+                                                 relation_decoder=relation_decoder))
+        self.other_drop_rates.pop("relation_decoder.transformerlayers.ffn_cfgs.ffn_drop", None)
         self.test_cfg, self.train_cfg = test_cfg, train_cfg
         assert len(self.in_channels) == 4 and num_transformer_feat_level == 3
         assert num_obj_query <= 256 and num_rel_query <= 128

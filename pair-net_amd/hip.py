@@ -129,6 +129,10 @@ _SIGS = {
     "pn_dilate2_f32": (C.c_int, [_vp, _vp] + [_i32] * 7 + [_vp]),
     "pn_subsample2_f32": (C.c_int, [_vp, _vp] + [_i32] * 6 + [_vp]),
     "pn_scale_rows_f32": (C.c_int, [_vp, _vp, _i64, _i64, _vp]),
+    "pn_dropout_f32": (C.c_int, [_vp, _vp, _vp, _i64, _f32, C.c_uint64, C.c_uint32, C.c_uint32,
+                                 C.c_uint32, _vp]),
+    "pn_dropout_keep_u8": (C.c_int, [_vp, _i64, _f32, C.c_uint64, C.c_uint32, C.c_uint32,
+                                     C.c_uint32, _vp]),
     "pn_layernorm_rows_bwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64,
                                             _i32, _f32, _vp]),
     "pn_gelu_f32": (C.c_int, [_vp, _vp, _i64, _vp]),
@@ -201,7 +205,7 @@ _SIGS = {
                                                 _i32, _vp]),
 }
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 30   # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
+ABI_VERSION = 31   # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
 
 _lib = None
 
@@ -1364,6 +1368,26 @@ def scale_rows(x, s):
     assert x.is_contiguous() and x.numel() % rows == 0
     _check(lib().pn_scale_rows_f32(_ptr(x), _ptr(s), rows, x.numel() // rows, _stream()),
            "pn_scale_rows_f32")
+
+
+# ---- the relation decoder's FFN dropout (csrc/dropout.hip; composed in grad.py) ------------------
+def dropout(x, out, p, seed, subseq, step, site, res=None):
+    """out = x * keep / (1 - p) (+ res); keep: Philox4x32-10 at counter (element / 4, subseq, site,
+    step) under key `seed`, regenerated by any later call with the same arguments (the backward
+    pass: the same call on the gradient).  out may be x."""
+    assert x.is_contiguous() and out.is_contiguous() and x.numel() == out.numel() and \
+        (res is None or (res.is_contiguous() and res.numel() == x.numel()))
+    _check(lib().pn_dropout_f32(_ptr(x), _ptr(res), _ptr(out), x.numel(), p, seed, subseq, step,
+                                site, _stream()), "pn_dropout_f32")
+
+
+def dropout_keep(n, p, seed, subseq, step, site, device=None):
+    """The keep bits `dropout` uses for n elements, as a uint8 tensor (1 = kept)."""
+    keep = torch.empty(n, device=device or torch.device("cuda", torch.cuda.current_device()),
+                       dtype=torch.uint8)
+    _check(lib().pn_dropout_keep_u8(_ptr(keep, torch.uint8), n, p, seed, subseq, step, site,
+                                    _stream()), "pn_dropout_keep_u8")
+    return keep
 
 
 # ---- Swin backbone backward (csrc/swin_grad.hip; composed in grad.py SwinBackboneGrad) ----------

@@ -25,6 +25,17 @@ overlapped with the backward pass (`dist.GradReducer`) -> global-norm clip coeff
 device -> ONE AdamW launch over the flat parameter buffer that the head's weight dict aliases ->
 refresh of the derived weight packs the inference kernels read.  No host synchronisation inside a
 step apart from the reference's own (the Hungarian cost matrices).
+
+Dropout.  The reference's config has ONE non-zero dropout rate, the Relation Fusion decoder's
+`ffn_drop=0.1` (configs/mask2former/pairnet.py:126): mmcv's FFN drops the hidden rows after the ReLU
+and the FFN's output before the shortcut, twelve `nn.Dropout` per iteration.  It is off by default
+(the deterministic step described above, launch for launch); `TailTrainer(head, dropout=True)`
+honours the configured rate (a float overrides it).  The taped forward then runs BEFORE the loss
+with the two dropouts per layer (csrc/dropout.hip: Philox4x32-10 keyed by `seed`, counter = (element
+/ 4, rank in `group`, site = 2 * layer + {0, 1}, `self.steps`); no mask stored, nothing uploaded),
+`head.loss` is handed the tape's dropped `rel` in place of the inference kernels' -- so `loss_r_cls`
+and d loss / d rel are those of the dropped logits, and nothing else of the outputs changes -- and
+the backward pass re-draws the same masks from the same counter.  The inference path never drops.
 """
 from collections import OrderedDict
 
@@ -32,7 +43,8 @@ import torch
 
 from . import hip
 from .dist import GradReducer
-from .grad import BackboneGrad, HeadGrad, PixelDecoderGrad, RelationTailGrad, SwinBackboneGrad
+from .grad import (BackboneGrad, FfnDropout, HeadGrad, PixelDecoderGrad, RelationTailGrad,
+                   SwinBackboneGrad)
 
 __all__ = ["TailTrainer", "step_lr"]
 
@@ -49,7 +61,7 @@ class TailTrainer:
     def __init__(self, head, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  max_norm=0.1, norm_decay_mult=0.0, lr_mult=None, group=None,
                  bucket_bytes=32 << 20, train_decoder=False, train_pixel_decoder=False,
-                 backbone=None, drop_path=False, seed=0):
+                 backbone=None, drop_path=False, seed=0, dropout=False):
         """`train_decoder`: also train the nine masked decoder layers, `query_feat`, `query_embed`
         and `level_embed` (`HeadGrad`; the reference's `transformer_decoder` group, lr_mult 0.1 by
         default here as in configs/mask2former/pairnet.py:358-363) -- everything of the head behind
@@ -68,6 +80,18 @@ class TailTrainer:
         self.swin = isinstance(backbone, SwinTransformerHip)
         self.drop_path = bool(drop_path) and self.swin
         self._gen = torch.Generator().manual_seed(int(seed))
+        # `dropout`: the Relation Fusion decoder's FFN dropout in train mode (mmcv FFN.layers' two
+        # nn.Dropout per layer; the reference's config sets ffn_drop=0.1 there and 0.0 everywhere
+        # else).  True: the configured rate (`head.rel_ffn_drop`); a float overrides it; False /
+        # 0.0 (default): the deterministic step, without a single extra launch.  The masks are
+        # drawn on the device by a counter-based generator (csrc/dropout.hip) from (`seed`, the
+        # rank in `group`, the step count, the site): nothing is stored or uploaded, ranks draw
+        # different masks from one seed, and a restored step count reproduces them.
+        self.seed = int(seed)
+        self.drop_p = self._dropout_rate(head, dropout)
+        import torch.distributed as dist
+        ini = dist.is_available() and dist.is_initialized()      # (as GradReducer reads `group`)
+        self.subseq = int(dist.get_rank(group)) if ini else 0
         train_pixel_decoder = bool(train_pixel_decoder) or backbone is not None
         self.train_pixel_decoder = bool(train_pixel_decoder)
         self.train_decoder = bool(train_decoder) or self.train_pixel_decoder
@@ -161,6 +185,31 @@ class TailTrainer:
         self._refresh_derived()
 
     # ------------------------------------------------------------------
+    @staticmethod
+    def _dropout_rate(head, dropout):
+        """The rate `dropout=` asks for; True reads the head's config and refuses one whose other
+        non-zero rates this step cannot honour."""
+        if dropout is True:
+            other = head.other_drop_rates
+            if other:
+                raise NotImplementedError(
+                    "dropout=True: the training step drops in the relation decoder's FFN only, but "
+                    "the config also sets " + ", ".join("%s=%g" % kv for kv in other.items()))
+            return float(head.rel_ffn_drop)
+        if dropout is False or dropout is None:
+            return 0.0
+        p = float(dropout)
+        if not 0.0 <= p < 1.0:
+            raise ValueError("dropout rate %r outside [0, 1)" % (dropout,))
+        return p
+
+    def dropout_descriptor(self, step=None):
+        """The `FfnDropout` of iteration `step` (default: the next one), or None when off."""
+        if self.drop_p == 0.0:
+            return None
+        return FfnDropout(self.drop_p, self.seed, self.subseq,
+                          self.steps if step is None else step)
+
     def _refresh_derived(self):
         """The weight packs the INFERENCE kernels read that are functions of trained parameters,
         rewritten in place (captured hipGraphs keep their pointers)."""
@@ -312,13 +361,27 @@ class TailTrainer:
                 feats[3] = self.bb_tape.forward(x4, keep).permute(0, 3, 1, 2)
         outs = head.forward(feats, img_metas)
         up = {}
-        losses = head.loss(*outs, gt_rels, None, gt_labels, gt_masks, img_metas,
-                           point_coords=point_coords, grads=up)
+        drop = self.dropout_descriptor()
+        if drop is None:
+            losses = head.loss(*outs, gt_rels, None, gt_labels, gt_masks, img_metas,
+                               point_coords=point_coords, grads=up)
         pl = head._last_plan
+        masks = outs[1]
+        if drop is not None and self.train_decoder and head.exact_mask_order == "full":
+            # (the dense cross-check mode re-computes each layer's mask logits into the plan's
+            # output buffer while taping; the loss below must see the final ones)
+            masks = dict(masks, mask=masks["mask"].clone())
         if self.train_decoder:
-            tape.forward_from_plan(pl, pl.sub_pos, pl.obj_pos)
+            tape.forward_from_plan(pl, pl.sub_pos, pl.obj_pos, dropout=drop)
         else:
-            tape.forward(pl.q, pl.sub_pos, pl.obj_pos)
+            tape.forward(pl.q, pl.sub_pos, pl.obj_pos, dropout=drop)
+        if drop is not None:
+            # the loss the reference optimises in train mode: on the DROPPED relation logits (the
+            # tape's); everything else of the outputs is the inference kernels'
+            cls = dict(outs[0])
+            cls["rel"] = tape.t["rel"]
+            losses = head.loss(cls, masks, gt_rels, None, gt_labels, gt_masks, img_metas,
+                               point_coords=point_coords, grads=up)
         if self.pd_tape is not None:
             self.pd_tape.forward(feats)
         self.reducer.start()

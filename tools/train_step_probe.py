@@ -4,8 +4,11 @@ tail alone, with the nine masked decoder layers, and with the pixel decoder's en
 well (everything behind the frozen backbone), and from the image with the ResNet-50's stages 2-4
 ("all": the reference's whole trainable graph), and where the time goes (HIP events around the
 phases of a step; the Hungarian assignments inside `loss` are host work as in the reference).
+`--dropout [RATE]` builds the trainers with the relation decoder's FFN dropout (no RATE: the config's
+0.1; DESIGN 7b: 24 more latency-sized launches per step), `--scopes tail,head` restricts the scopes.
 Prints one JSON line.  `rocprofv3 --kernel-trace --stats -- python tools/train_step_probe.py`
 gives the per-kernel view (profiles/r06_train_step_kernel_stats.csv)."""
+import argparse
 import json
 import os
 import sys
@@ -19,7 +22,14 @@ from pairnet_amd import CrossHead2, ResNet50Hip, TailTrainer, pairnet_head_cfg  
 
 dev = torch.device("cuda:0")
 torch.cuda.set_device(dev)
-steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+ap = argparse.ArgumentParser()
+ap.add_argument("steps", nargs="?", type=int, default=10)
+ap.add_argument("--dropout", nargs="?", const=True, default=None,
+                type=lambda v: float(v), help="train with the relation decoder's FFN dropout")
+ap.add_argument("--scopes", default="tail,head,head+pixel_decoder,all")
+args = ap.parse_args()
+steps = args.steps
+trainer_kw = {} if args.dropout is None else dict(dropout=args.dropout)
 cfg = pairnet_head_cfg()
 cfg.pop("type")
 head = CrossHead2(**cfg)
@@ -46,10 +56,12 @@ out = {"what": "TailTrainer.step, 800x1333, one image, frozen ResNet-50 features
                "counted under `backward`); "
                "ms per step over %d steps (device wait at both ends) and the phases of one step "
                "(HIP events; `loss` includes the two Hungarian assignments on the host)" % steps}
-for scope in ("tail", "head", "head+pixel_decoder", "all"):
+out["dropout"] = args.dropout if args.dropout is not None else False
+for scope in args.scopes.split(","):
     mode = scope != "tail"
     tr = TailTrainer(head, train_decoder=mode, train_pixel_decoder=scope == "head+pixel_decoder",
-                     backbone=net if scope == "all" else None)
+                     backbone=net if scope == "all" else None, **trainer_kw)
+    drop = tr.dropout_descriptor() if trainer_kw else None
     inp = img if scope == "all" else feats
     for _ in range(3):
         vals = tr.step(inp, metas, gt_rels, gt_labels, gt_masks, point_coords=pts)
@@ -69,13 +81,18 @@ for scope in ("tail", "head", "head+pixel_decoder", "all"):
         outs = head.forward(feats, metas)
         ev[1].record()
         up = {}
-        head.loss(*outs, gt_rels, None, gt_labels, gt_masks, metas, point_coords=pts, grads=up)
+        if drop is None:
+            head.loss(*outs, gt_rels, None, gt_labels, gt_masks, metas, point_coords=pts, grads=up)
         ev[2].record()
         pl = head._last_plan
+        tape_kw = {} if drop is None else dict(dropout=drop)
         if mode:
-            tr.tape.forward_from_plan(pl, pl.sub_pos, pl.obj_pos)
+            tr.tape.forward_from_plan(pl, pl.sub_pos, pl.obj_pos, **tape_kw)
         else:
-            tr.tape.forward(pl.q, pl.sub_pos, pl.obj_pos)
+            tr.tape.forward(pl.q, pl.sub_pos, pl.obj_pos, **tape_kw)
+        if drop is not None:      # the loss of the DROPPED logits: counted under `taped_forward`
+            head.loss(dict(outs[0], rel=tr.tape.t["rel"]), outs[1], gt_rels, None, gt_labels,
+                      gt_masks, metas, point_coords=pts, grads=up)
         if tr.pd_tape is not None:
             tr.pd_tape.forward(feats)
         ev[3].record()
