@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PN_ABI_VERSION 31
+#define PN_ABI_VERSION 32
 int pn_abi_version(void);
 
 /* ------------------------------------------------------------------------- *
@@ -606,6 +606,46 @@ int pn_pan_masks_u8(const uint8_t* rgb, const int* ids, const int* cats, uint8_t
 int pn_preprocess_u8_f32(const uint8_t* img, int H, int W, float* out, int Hn, int Wn, int Hp,
                          int Wp, const float* mean3, const float* stdinv3, int to_rgb,
                          void* stream);
+
+/* Train-time input pipeline (configs/mask2former/pairnet.py:234-306: RandomFlip -> AutoAugment
+ * [policy 1: Resize | policy 2: Resize -> RelRandomCrop -> Resize] -> Normalize -> Pad ->
+ * RelsFormatBundle -> collate at samples_per_gpu=2).  The draws and the boxes are host work; each
+ * entry below refuses (-1) null pointers, non-positive sizes, a window outside the resized image,
+ * misaligned bases and a batch tensor smaller than the image.
+ *
+ * The LAST Resize -> Normalize -> Pad -> collate of one image (pairnet.py:247-266 / :280-298,
+ * :302-303; mmcv.imresize = OpenCV INTER_LINEAR on uint8, the arithmetic of
+ * pn_preprocess_u8_f32) with RandomFlip (:243; mmcv.imflip, horizontal) folded in as a column
+ * permutation of the source:
+ *   img [H][W][3] uint8 BGR: the decoded image (policy 1) or the window below (policy 2, flip 0)
+ *   out: base of the float32 batch tensor [k][3][Hmax][Wmax]; image `slot` is written at
+ *        out + slot * batch_stride (elements, >= 3 Hmax Wmax), zero beyond (Hn, Wn) */
+int pn_augment_image_u8_f32(const uint8_t* img, int H, int W, int flip, float* out,
+                            int64_t batch_stride, int slot, int Hn, int Wn, int Hmax, int Wmax,
+                            const float* mean3, const float* stdinv3, int to_rgb, void* stream);
+
+/* Policy 2's first Resize (pairnet.py:268-273) of the optionally flipped image, evaluated on
+ * the crop window of RelRandomCrop only (pairnet/datasets/pipelines/rel_randomcrop.py:27-39):
+ *   out [ch][cw][3] uint8, out(y, x) = pixel (y + oy, x + ox) of the [H1][W1] resize;
+ *   0 <= oy, oy + ch <= H1, 0 <= ox, ox + cw <= W1. */
+int pn_augment_resize_crop_u8(const uint8_t* img, int H, int W, int flip, int H1, int W1, int oy,
+                              int ox, uint8_t* out, int ch, int cw, void* stream);
+
+/* Every mask stage of the training pipeline in one gather: the loader
+ * (pairnet/datasets/pipelines/loading.py:128-147: rgb2id(PNG) == id), RandomFlip, the
+ * BitmapMasks.rescale of both Resizes (OpenCV INTER_NEAREST: source index
+ * min(floor(dst * (1.0 / ((double)dst_size / src_size))), src_size - 1), doubles),
+ * RelRandomCrop's mask crop (rel_randomcrop.py:76-81), Pad, collate, and `PSGTr.forward_train`'s
+ * pad to the batch tensor + nearest resize to half size (frameworks/psgtr.py:126-141, the
+ * arithmetic of pn_gt_mask_prepare_u8):
+ *   png [H0][W0][3] uint8 RGB            ids [Gk] int32: the segments the crop kept, Gk <= 256
+ *   (H1, W1): first Resize; window (oy, ox, ch, cw) inside it; (H2, W2): second Resize of the
+ *   window.  Policy 1: window = (0, 0, H1, W1) and (H2, W2) = (H1, W1).
+ *   out [Gk][Hb / 2][Wb / 2] uint8 0/1, (Hb, Wb) >= (H2, W2) the batch tensor's size.
+ * png, ids and out 4-byte aligned. */
+int pn_augment_masks_u8(const uint8_t* png, int H0, int W0, const int* ids, int Gk, int flip,
+                        int H1, int W1, int oy, int ox, int ch, int cw, int H2, int W2, int Hb,
+                        int Wb, uint8_t* out, void* stream);
 
 /* Evaluator feed (pairnet/evaluation/sgg_metrics.py:1276-1380, mask_iou :1374-1380):
  * masks as bit rows (bit i of word w = pixel 64w+i) and the exact integer counts

@@ -2,7 +2,7 @@
 from .config import (ConfigDict, baseline_head_cfg, baseline_r50, bbox_head_cfg,  # noqa: F401
                      channel_mapper_cfg, cross_r101_vg, load_config,
                      pairnet_head_cfg, pairnet_r50, pairnet_swin, psgtr2_head_cfg, psgtr2_r50,
-                     swin_backbone_cfg, test_pipeline_cfg)
+                     swin_backbone_cfg, test_pipeline_cfg, train_pipeline_cfg)
 from .psgtr_head2 import PSGTrHead2  # noqa: F401
 from .backbone import ResNet50Hip  # noqa: F401
 from .swin import SwinTransformerHip  # noqa: F401
@@ -15,6 +15,7 @@ from .grad import (BackboneGrad, FfnDropout, HeadGrad, PixelDecoderGrad,  # noqa
                    RelationTailGrad, SwinBackboneGrad)
 from .train import TailTrainer  # noqa: F401
 from .preprocess import TestPipeline  # noqa: F401
+from .train_pipeline import AugParams, HalfSizeMasks, TrainPipeline  # noqa: F401
 from .detector import (PSGTr, Result, ResultStreamer, build_detector, load_checkpoint,  # noqa: F401
                        triplet2Result)
 from .dist import all_gather_triplets, shard_indices  # noqa: F401
@@ -27,4 +28,5 @@ __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "Cros
            "baseline_r50", "PSGTrHead2", "psgtr2_head_cfg", "psgtr2_r50", "ResNet50Hip",
            "SwinTransformerHip", "pairnet_swin", "swin_backbone_cfg", "TestPipeline", "test_pipeline_cfg",
            "CrossHeadBBox", "ChannelMapper", "bbox_head_cfg", "channel_mapper_cfg", "cross_r101_vg",
-           "TripletEvaluator", "SceneGraphMetrics", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "TailTrainer", "FfnDropout"]
+           "TripletEvaluator", "SceneGraphMetrics", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "TailTrainer", "FfnDropout",
+           "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg"]

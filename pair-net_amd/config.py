@@ -288,6 +288,34 @@ def test_pipeline_cfg():
 test_pipeline_cfg.__test__ = False
 
 
+TRAIN_SCALES = [(s, 1333) for s in range(480, 801, 32)]
+
+
+def train_pipeline_cfg():
+    """`train_pipeline` of configs/mask2former/pairnet.py:234-306 (what
+    train_pipeline.TrainPipeline.from_config consumes): flip, then one of two policies -- a
+    multi-scale Resize, or Resize -> RelRandomCrop -> Resize -- then Normalize, Pad, format."""
+    multi = lambda scales, **kw: dict(type="Resize", img_scale=list(scales),
+                                      multiscale_mode="value", **kw)
+    return [
+        dict(type="LoadImageFromFile"),
+        dict(type="LoadPanopticSceneGraphAnnotations", with_bbox=True, with_rel=True,
+             with_mask=True, with_seg=True),
+        dict(type="RandomFlip", flip_ratio=0.5),
+        dict(type="AutoAugment", policies=[
+            [multi(TRAIN_SCALES, keep_ratio=True)],
+            [multi([(400, 1333), (500, 1333), (600, 1333)], keep_ratio=True),
+             dict(type="RelRandomCrop", crop_type="absolute_range", crop_size=(384, 600),
+                  allow_negative_crop=False),
+             multi(TRAIN_SCALES, override=True, keep_ratio=True)],
+        ]),
+        dict(type="Normalize", **IMG_NORM_CFG),
+        dict(type="Pad", size_divisor=1),
+        dict(type="RelsFormatBundle"),
+        dict(type="Collect", keys=["img", "gt_bboxes", "gt_labels", "gt_rels", "gt_masks"]),
+    ]
+
+
 def load_config(path):
     """exec a reference-format python config; returns ConfigDict of its globals
     (without `_base_` inheritance: the model section of pairnet.py has none)."""

@@ -4,7 +4,7 @@
 // (Q x G and R x G floats) go to the host, where the reference solves them too (`cost.cpu()`,
 // matcher.py:262-264).  All of it is a few hundred KB per image: latency-sized kernels, fp32
 // arithmetic in the reference's formulas, deterministic reductions (fixed order).
-#include "common.h"
+#include "pixel_maps.h"
 
 __device__ __forceinline__ float block_sum(float v, float* red) {   // <= 1024 threads
   v = wave_sum(v);
@@ -37,8 +37,7 @@ __global__ __launch_bounds__(256) void k_gt_mask_prepare(const uint8_t* __restri
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, g = blockIdx.z;
   if (x >= Wo) return;
   const float sy_f = (float)H / (float)Ho, sx_f = (float)W / (float)Wo;
-  const int sy = min((int)floorf((float)y * sy_f), H - 1);
-  const int sx = min((int)floorf((float)x * sx_f), W - 1);
+  const int sy = aten_nearest(y, sy_f, H), sx = aten_nearest(x, sx_f, W);
   out[((int64_t)g * Ho + y) * Wo + x] =
       (sy < h && sx < w) ? in[((int64_t)g * h + sy) * w + sx] : (uint8_t)0;
 }

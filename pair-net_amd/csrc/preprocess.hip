@@ -9,20 +9,7 @@
 // horizontal pass, vertical pass ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2.
 // Integer arithmetic: bit-exact against oracle/preprocess.py.  (cv2 is not in this image:
 // unpinned against OpenCV itself.)
-#include "common.h"
-
-__device__ __forceinline__ void lin_coef(int d, double scale, int n, int& s, int& a0, int& a1,
-                                         bool horizontal) {
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  s = (int)floorf(f);
-  f -= (float)s;
-  if (horizontal) {
-    if (s < 0) { f = 0.f; s = 0; }
-    if (s >= n - 1) { f = 0.f; s = n - 1; }
-  }
-  a0 = (int)rintf((1.f - f) * 2048.f);
-  a1 = (int)rintf(f * 2048.f);
-}
+#include "pixel_maps.h"
 
 __global__ __launch_bounds__(256) void k_preprocess(const uint8_t* __restrict__ img, int H,
                                                     int W, float* __restrict__ out, int Hn,
@@ -49,12 +36,10 @@ __global__ __launch_bounds__(256) void k_preprocess(const uint8_t* __restrict__ 
   const float mean[3] = {m0, m1, m2}, stdinv[3] = {s0, s1, s2};
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const int h0 = (int)r0[sx * 3 + c] * ax0 + (int)r0[x1 * 3 + c] * ax1;
-    const int h1 = (int)r1[sx * 3 + c] * ax0 + (int)r1[x1 * 3 + c] * ax1;
-    const int v = (((by0 * (h0 >> 4)) >> 16) + ((by1 * (h1 >> 4)) >> 16) + 2) >> 2;
-    const int u = min(max(v, 0), 255);
+    const int u = lin_blend_u8(r0[sx * 3 + c], r0[x1 * 3 + c], r1[sx * 3 + c], r1[x1 * 3 + c],
+                               ax0, ax1, by0, by1);
     const int oc = to_rgb ? 2 - c : c;       // BGR -> RGB; mean / std are in OUTPUT order
-    out[oc * plane + e] = __fmul_rn(__fsub_rn((float)u, mean[oc]), stdinv[oc]);
+    out[oc * plane + e] = normalize_u8(u, mean[oc], stdinv[oc]);
   }
 }
 

@@ -515,6 +515,7 @@ class PSGTr:
         """PSGTr.forward_train's ground-truth mask preparation (psgtr.py:126-141): zero-pad to the
         batch tensor's (H, W), nearest-resize to (H // 2, W // 2); one kernel per image."""
         from . import hip
+        from .train_pipeline import HalfSizeMasks
         if not getattr(self.bbox_head, "use_mask", True):
             return gt_masks
         assert gt_masks is not None
@@ -523,6 +524,16 @@ class PSGTr:
         prepared = []
         with torch.cuda.device(dev):
             for each in gt_masks:
+                if isinstance(each, HalfSizeMasks):
+                    # (train_pipeline.TrainPipeline wrote them at half size already)
+                    m = each.masks
+                    if each.batch_shape != (H, W) or m.dim() != 3 or m.dtype != torch.uint8 or \
+                            tuple(m.shape[1:]) != (H // 2, W // 2) or not m.is_cuda:
+                        raise ValueError("gt_masks: HalfSizeMasks (device uint8 [G, %d, %d]) for a "
+                                         "(%d, %d) batch tensor, got %s for %s"
+                                         % (H // 2, W // 2, H, W, tuple(m.shape), each.batch_shape))
+                    prepared.append(m)
+                    continue
                 m = each.to_ndarray() if hasattr(each, "to_ndarray") else each
                 m = torch.as_tensor(m).to(dev)
                 if m.dtype not in (torch.bool, torch.uint8):

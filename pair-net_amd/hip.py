@@ -190,6 +190,10 @@ _SIGS = {
     "pn_pan_masks_u8": (C.c_int, [_vp] * 5 + [_i32] * 3 + [_vp]),
     "pn_preprocess_u8_f32": (C.c_int, [_vp, _i32, _i32, _vp] + [_i32] * 4 + [C.POINTER(_f32),
                                                                             C.POINTER(_f32), _i32, _vp]),
+    "pn_augment_image_u8_f32": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64] + [_i32] * 5
+                                + [C.POINTER(_f32), C.POINTER(_f32), _i32, _vp]),
+    "pn_augment_resize_crop_u8": (C.c_int, [_vp] + [_i32] * 7 + [_vp, _i32, _i32, _vp]),
+    "pn_augment_masks_u8": (C.c_int, [_vp, _i32, _i32, _vp] + [_i32] * 12 + [_vp, _vp]),
     "pn_pack_mask_bits": (C.c_int, [_vp, _vp, _i64, _i64, _vp]),
     "pn_mask_iou_counts": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
     "pn_zero_rows_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _i64, _i64, _vp]),
@@ -205,7 +209,7 @@ _SIGS = {
                                                 _i32, _vp]),
 }
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 31   # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
+ABI_VERSION = 32   # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
 
 _lib = None
 
@@ -1050,6 +1054,44 @@ def preprocess_u8(img, H, W, out, Hn, Wn, Hp, Wp, mean, stdinv, to_rgb):
     s = (_f32 * 3)(*[float(v) for v in stdinv])
     _check(lib().pn_preprocess_u8_f32(_ptr(img, torch.uint8), H, W, _ptr(out), Hn, Wn, Hp, Wp,
                                       m, s, int(to_rgb), _stream()), "pn_preprocess_u8_f32")
+
+
+# ---- train-time input pipeline (csrc/augment.hip) ----
+def augment_image(img, H, W, flip, batch, slot, Hn, Wn, mean, stdinv, to_rgb):
+    """img [H][W][3] uint8 -> image `slot` of the float32 batch tensor [k][3][Hmax][Wmax]: the last
+    Resize of the (flipped) image -> Normalize -> zero Pad up to (Hmax, Wmax)."""
+    k, c, Hmax, Wmax = batch.shape
+    assert c == 3 and batch.is_contiguous() and 0 <= slot < k and img.is_contiguous()
+    m = (_f32 * 3)(*[float(v) for v in mean])
+    s = (_f32 * 3)(*[float(v) for v in stdinv])
+    _check(lib().pn_augment_image_u8_f32(_ptr(img, torch.uint8), H, W, int(flip), _ptr(batch),
+                                         3 * Hmax * Wmax, slot, Hn, Wn, Hmax, Wmax, m, s,
+                                         int(to_rgb), _stream()), "pn_augment_image_u8_f32")
+
+
+def augment_resize_crop(img, H, W, flip, H1, W1, oy, ox, out):
+    """out [ch][cw][3] uint8 = the window at (oy, ox) of the [H1][W1] resize of the (flipped)
+    img."""
+    ch, cw, c = out.shape
+    assert c == 3 and out.is_contiguous() and img.is_contiguous()
+    _check(lib().pn_augment_resize_crop_u8(_ptr(img, torch.uint8), H, W, int(flip), H1, W1, oy, ox,
+                                           _ptr(out, torch.uint8), ch, cw, _stream()),
+           "pn_augment_resize_crop_u8")
+
+
+def augment_masks(png, ids, flip, size1, window, size2, batch_size, out):
+    """png [H0][W0][3] uint8 RGB, ids [Gk] int32 -> out [Gk][Hb // 2][Wb // 2] uint8: the masks of
+    the kept segments after flip, Resize to `size1`, crop `window` = (oy, ox, ch, cw), Resize to
+    `size2`, pad to `batch_size` = (Hb, Wb) and the loss side's nearest half-size resize."""
+    H0, W0, c = png.shape
+    Gk, (Hb, Wb) = int(ids.shape[0]), batch_size
+    assert c == 3 and png.is_contiguous() and out.is_contiguous()
+    assert tuple(out.shape) == (Gk, Hb // 2, Wb // 2)
+    oy, ox, ch, cw = window
+    _check(lib().pn_augment_masks_u8(_ptr(png, torch.uint8), H0, W0, _ptr(ids, torch.int32), Gk,
+                                     int(flip), size1[0], size1[1], oy, ox, ch, cw, size2[0],
+                                     size2[1], Hb, Wb, _ptr(out, torch.uint8), _stream()),
+           "pn_augment_masks_u8")
 
 
 def pack_mask_bits(masks_u8, words, rows, HW):

@@ -1,0 +1,244 @@
+"""GPU: the train-time input pipeline (csrc/augment.hip, pairnet_amd.TrainPipeline) against the
+staged CPU pipeline of tests/train_pipeline_ref.py -- byte / integer work and float arithmetic
+in the oracle's operation order: every comparison is exact."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import train_pipeline_ref as R
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+SCALES = [(48, 80), (56, 80)]
+
+
+def _pipe(scales=SCALES, first=((40, 80), (48, 80)), crop=(20, 40), allow_negative=False, **kw):
+    from pairnet_amd import TrainPipeline
+    return TrainPipeline([dict(scales1=list(scales), crop=None, scales2=None),
+                          dict(scales1=list(first), crop=dict(size=crop, allow_negative=allow_negative),
+                               scales2=list(scales))], device=DEV, **kw)
+
+
+def _params(flip, scale1, crop=None, scale2=None):
+    from pairnet_amd import AugParams
+    return AugParams(flip, 0 if crop is None else 1, scale1, crop, scale2)
+
+
+# name: (sample (seed, H, W), flip, scale1, crop (ch, cw, oy, ox), scale2,
+#        batch tensor (Hb, Wb) or None = the image's own size, kept segments or None = all)
+CASES = {
+    # 48 x 69 -> half size 24 x 34: rows of 34 bytes, not 4-aligned; planes of 816 are
+    "p1_unaligned_png": ((9, 37, 53), False, (48, 80), None, None, None, None),
+    # 56 x 80 inside an odd 61 x 87 batch tensor -> 30 x 43 (both floors, planes of 1290 bytes:
+    # the byte-store path), the padding region non-empty
+    "p1_flip_odd_batch": ((9, 37, 53), True, (56, 80), None, None, (61, 87), None),
+    # policy 2, the window touches the right and the bottom border of the 48 x 69 resize
+    "p2_flip_border_crop": ((9, 37, 53), True, (48, 80), (24, 30, 24, 39), (56, 80), None, None),
+    # everything 4-aligned: 40 x 64 PNG, 64 x 96 batch tensor -> 32 x 48
+    "p2_aligned": ((3, 40, 64), False, (48, 80), (20, 40, 5, 7), (48, 80), (64, 96), None),
+    # 6 -> 34 rows: the axis where OpenCV's nearest index is not floor(x * src / dst)
+    "p1_6_to_34": ((5, 6, 9), False, (1000, 34), None, None, None, None),
+    "p1_flip_6_to_34": ((5, 6, 9), True, (1000, 34), None, None, (35, 52), None),
+    # one kept segment; the last segment of this entry is absent from its PNG
+    "p2_one_segment": ((9, 37, 53), False, (40, 80), (22, 33, 3, 9), (56, 80), (57, 80), [1]),
+    "p1_absent_segment": ((9, 37, 53), True, (48, 80), None, None, (50, 70), [5, 0]),
+}
+
+
+def _case(name):
+    (seed, H, W), flip, scale1, crop, scale2, batch_shape, only = CASES[name]
+    img, pan, ann = R.synthetic_sample(seed, H=H, W=W)
+    p = _params(flip, scale1, crop, scale2)
+    pipe = _pipe(allow_negative=True)       # (the kernels are tested on any window)
+    geo = pipe.geometry(H, W, p)
+    return img, pan, ann, p, pipe, geo, batch_shape or geo["pad"], only
+
+
+def test_the_cases_cover_what_they_claim():
+    sizes = {}
+    for name in CASES:
+        img, pan, ann, p, pipe, geo, (Hb, Wb), only = _case(name)
+        sizes[name] = (geo["size2"], (Hb, Wb))
+        assert Hb >= geo["size2"][0] and Wb >= geo["size2"][1]
+    assert sizes["p1_unaligned_png"] == ((48, 69), (48, 69))
+    assert sizes["p1_flip_odd_batch"][0] == (56, 80)
+    assert sizes["p1_6_to_34"][0] == (34, 51)
+    geo = _case("p2_flip_border_crop")[5]
+    oy, ox, ch, cw = geo["window"]
+    assert (oy + ch, ox + cw) == geo["size1"] == (48, 69)
+    _, pan, ann, *_ = _case("p1_absent_segment")
+    ids = [m["id"] for m in ann["masks"]]
+    seg = R.OD.rgb2id(pan)
+    assert max(ids) > 2 ** 16 and not (seg == ids[5]).any() and (seg == ids[0]).any()
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_fused_mask_kernel_equals_the_staged_pipeline(name):
+    from pairnet_amd import hip
+    img, pan, ann, p, pipe, geo, (Hb, Wb), only = _case(name)
+    want = R.staged_sample(img, pan, ann, p, allow_negative_crop=True)
+    keep = pipe.targets(ann, p, geo)["keep"]
+    assert np.array_equal(keep, want["keep"])
+    rows = np.arange(len(keep)) if only is None else np.array(
+        [int(np.nonzero(keep == g)[0][0]) for g in only])
+    ids = torch.tensor([ann["masks"][int(keep[r])]["id"] for r in rows], dtype=torch.int32, device=DEV)
+    full = want["masks"][rows]
+    assert full.shape[1:] == geo["size2"]
+    expect = R.forward_train_masks(full, Hb, Wb)
+    out = torch.full((len(rows), Hb // 2, Wb // 2), 7, dtype=torch.uint8, device=DEV)
+    guard = torch.full((64,), 9, dtype=torch.uint8, device=DEV)       # (allocated right behind)
+    hip.augment_masks(torch.from_numpy(pan).to(DEV), ids, p.flip, geo["size1"], geo["window"],
+                      geo["size2"], (Hb, Wb), out)
+    torch.cuda.synchronize()
+    assert torch.equal(out.cpu(), expect)
+    assert bool((guard == 9).all())
+    assert expect.any() or name == "p1_6_to_34" or only is not None
+    # ... and through the existing preparation of the full-size masks
+    via = torch.empty_like(out)
+    hip.gt_mask_prepare(torch.from_numpy(full).to(DEV), via, Hb, Wb)
+    assert torch.equal(out, via)
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_image_kernels_equal_the_staged_pipeline(name):
+    from pairnet_amd import hip
+    img, pan, ann, p, pipe, geo, (Hb, Wb), only = _case(name)
+    want = R.staged_sample(img, pan, ann, p, allow_negative_crop=True)
+    (H, W), (H1, W1), (H2, W2) = geo["ori"], geo["size1"], geo["size2"]
+    oy, ox, ch, cw = geo["window"]
+    src = torch.from_numpy(np.ascontiguousarray(img)).to(DEV)
+    batch = torch.full((3, 3, Hb, Wb), float("nan"), device=DEV)
+    if p.crop is None:
+        hip.augment_image(src, H, W, p.flip, batch, 1, H2, W2, pipe._mean[0], pipe._mean[1], True)
+    else:
+        win = torch.full((ch, cw, 3), 3, dtype=torch.uint8, device=DEV)
+        hip.augment_resize_crop(src, H, W, p.flip, H1, W1, oy, ox, win)
+        assert np.array_equal(win.cpu().numpy(), want["window_u8"])
+        hip.augment_image(win, ch, cw, False, batch, 1, H2, W2, pipe._mean[0], pipe._mean[1], True)
+    torch.cuda.synchronize()
+    expect = np.zeros((3, Hb, Wb), np.float32)
+    expect[:, :H2, :W2] = want["img"]
+    assert want["img"].shape == (3, H2, W2)
+    assert np.array_equal(batch[1].cpu().numpy(), expect)
+    assert bool(torch.isnan(batch[0]).all()) and bool(torch.isnan(batch[2]).all())
+
+
+@pytest.mark.parametrize("h,w,scale,div", [(37, 53, (80, 48), 1), (40, 64, (96, 56), 32)])
+def test_final_stage_without_flip_equals_the_test_pipeline(h, w, scale, div):
+    from pairnet_amd import TestPipeline, hip
+    from test_preprocess import _image
+    img = torch.from_numpy(np.ascontiguousarray(_image(11, h, w))).to(DEV)
+    tp = TestPipeline(img_scale=scale, size_divisor=div, device=DEV)
+    ref, metas = tp(img)
+    (Hn, Wn), (Hp, Wp) = tp.sizes(h, w)
+    out = torch.full((1, 3, Hp, Wp), float("nan"), device=DEV)
+    hip.augment_image(img, h, w, False, out, 0, Hn, Wn, tp._mean[0], tp._mean[1], True)
+    assert torch.equal(out, ref)
+
+
+def _prepare(img, gt_masks):
+    """`PSGTr._prepare_gt_masks` without building a detector around it."""
+    from pairnet_amd import PSGTr
+    fake = types.SimpleNamespace(bbox_head=types.SimpleNamespace(use_mask=True,
+                                                                 device=torch.device(DEV)))
+    return PSGTr._prepare_gt_masks(fake, img, gt_masks)
+
+
+def _two_samples():
+    a = R.synthetic_sample(9, hand_placed=True)                       # 37 x 53, 6 segments
+    b = R.synthetic_sample(3, H=40, W=64, hand_placed=True)           # 40 x 64, 4 segments
+    pa = _params(True, (48, 80), (24, 30, 24, 39), (56, 80))          # policy 2 -> 56 x 70
+    pb = _params(False, (56, 80))                                     # policy 1 -> 50 x 80
+    return [a, b], [pa, pb]
+
+
+def test_batch_equals_the_collated_staged_pipeline():
+    pipe = _pipe()
+    samples, params = _two_samples()
+    staged = [R.staged_sample(*s, p) for s, p in zip(samples, params)]
+    want = R.collate(staged)
+    got = pipe.batch(samples, slot=0, params=params)
+    torch.cuda.synchronize()
+    assert set(got) == set(want) and got["img"].shape == want["img"].shape == (2, 3, 56, 80)
+    assert staged[0]["masks"].shape == (3, 56, 70) and staged[1]["masks"].shape == (4, 50, 80)
+    assert torch.equal(got["img"].cpu(), want["img"])
+    for k in ("gt_bboxes", "gt_labels", "gt_rels"):
+        for a, b in zip(got[k], want[k]):
+            assert a.dtype == b.dtype and torch.equal(a, b), k
+    assert got["gt_rels"][0].dtype == torch.int64 and got["gt_rels"][1].dtype == torch.int32
+    assert all(R.metas_equal(a, b) for a, b in zip(got["img_metas"], want["img_metas"]))
+    assert got["img_metas"][0]["flip_direction"] == "horizontal" and not got["img_metas"][1]["flip"]
+    prepared = _prepare(got["img"], want["gt_masks"])                # the existing path
+    passed = _prepare(got["img"], got["gt_masks"])                   # the marker passes through
+    for m, a, b in zip(got["gt_masks"], passed, prepared):
+        assert a is m.masks and m.batch_shape == (56, 80)
+        assert a.dtype == b.dtype and torch.equal(a, b) and bool(b.any())
+    from pairnet_amd import HalfSizeMasks
+    with pytest.raises(ValueError):
+        _prepare(got["img"][:, :, :54], got["gt_masks"])
+    with pytest.raises(ValueError):
+        _prepare(got["img"], [HalfSizeMasks(passed[0][:, :-1], (56, 80))])
+
+
+def test_batch_reuses_its_slot_and_reports_a_crop_without_relations():
+    pipe = _pipe()
+    samples, params = _two_samples()
+    dev = [(torch.from_numpy(np.ascontiguousarray(i)).to(DEV), torch.from_numpy(p).to(DEV), a)
+           for i, p, a in samples]
+    first = pipe.batch(dev, slot=1, params=params)
+    keep = first["img"].clone()
+    torch.cuda.synchronize()
+    count = lambda: torch.cuda.memory_stats(DEV)["allocation.all.allocated"]
+    before = count()
+    small = pipe.batch(dev[1:], slot=1, params=params[1:])
+    assert count() == before                                          # nothing allocated
+    assert small["img"].shape == (1, 3, 50, 80)
+    assert small["img"].data_ptr() == first["img"].data_ptr()
+    assert torch.equal(small["img"][0], keep[1, :, :50])
+    other = pipe.batch(dev, slot=2, params=params)                    # another slot, other memory
+    assert other["img"].data_ptr() != first["img"].data_ptr()
+    # a crop that keeps one box keeps no relation: nothing is launched, the caller redraws
+    none = _params(False, (48, 80), (20, 20, 0, 16), (48, 80))
+    assert R.staged_sample(*samples[0], none) is None
+    before = count()
+    assert pipe.batch(dev, slot=1, params=[none, params[1]]) is None and pipe.rejected == [0]
+    assert pipe(*dev[0], params=none) is None and count() == before
+    one = pipe(*dev[0], params=params[0], slot=3)
+    assert one["img"].shape == (1, 3, 56, 70) and torch.equal(one["img"][0], keep[0, :, :, :70])
+    drawn = pipe.batch(dev, slot=4, rng=np.random.RandomState(0))     # (the draws, end to end)
+    assert drawn is None or len(drawn["gt_masks"]) == 2
+
+
+def test_detector_train_step_takes_the_batch():
+    """`det.train_step(pipe.batch(...), None)` on the R50 detector: finite loss terms and
+    grad_norm; the marker-wrapped masks and the staged full-size masks give identical prepared
+    tensors (the tensors are compared, not a second optimizer trajectory)."""
+    from pairnet_amd import build_detector, pairnet_r50
+    det = build_detector(pairnet_r50())
+    det.bbox_head.init_weights(seed=4)
+    det.to(DEV)
+    pipe = _pipe(scales=[(96, 160), (112, 160)], first=[(96, 160)], crop=(40, 90))
+    samples = _two_samples()[0]
+    params = [_params(True, (96, 160), (60, 80, 0, 0), (112, 160)), _params(False, (96, 160))]
+    batch = pipe.batch(samples, params=params)
+    staged = [R.staged_sample(*s, p) for s, p in zip(samples, params)]
+    Hb, Wb = batch["img"].shape[2:]
+    assert (Hb, Wb) == tuple(R.collate(staged)["img"].shape[2:]) == (112, 154)
+    a = det._prepare_gt_masks(batch["img"], batch["gt_masks"])
+    b = det._prepare_gt_masks(batch["img"], [s["masks"] for s in staged])
+    assert all(torch.equal(x, y) and bool(x.any()) for x, y in zip(a, b))
+    rec = det.train_step(batch, None)
+    assert set(rec) == {"loss", "log_vars", "num_samples"} and rec["num_samples"] == 2
+    terms = {k: v for k, v in rec["log_vars"].items()}
+    assert {"loss_r_cls", "loss_sub_cls", "loss_obj_cls", "loss_match", "grad_norm"} <= set(terms)
+    assert all(np.isfinite(v) for v in terms.values()) and terms["grad_norm"] > 0
+
+
+def test_bad_arguments_are_refused_without_a_launch():
+    from pairnet_amd import hip
+    torch.cuda.synchronize()
+    R.check_bad_arguments(hip.lib())
+    torch.cuda.synchronize()            # (a launch on one of those addresses would fault here)
