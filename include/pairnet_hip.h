@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PN_ABI_VERSION 32
+#define PN_ABI_VERSION 33
 int pn_abi_version(void);
 
 /* ------------------------------------------------------------------------- *
@@ -811,6 +811,41 @@ int pn_bce_posw_mean_grad_f32(const float* logits, const float* target, float* g
                               float loss_weight, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Loss targets on the device (csrc/assign.hip, ABI 33): the two Hungarian assignments and the index
+ * bookkeeping of `_get_target_single`, so that a training step does not wait for the host.
+ * ------------------------------------------------------------------------- */
+/* Batched rectangular linear sum assignment: what `linear_sum_assignment(cost.cpu())` returns at
+ * approaches/matcher.py:262-264 (IdMatcher) and in [3P] mmdet mask_hungarian_assigner.py
+ * (MaskHungarianAssigner.assign; both called from pairnet_head.py:645-718), for P problems in one
+ * launch, one wavefront each.  scipy's algorithm (shortest augmenting paths on float64 duals over the
+ * fp32 costs) step for step: row_ind / col_ind EQUAL scipy's, ties included.
+ *   cost [cost_len] fp32; table [P][4] int64 on the device = {offset of the row-major rows x cols
+ *   matrix in cost, rows, cols, offset of the problem's min(rows, cols) output entries};
+ *   row_ind (ascending) / col_ind [out_len] int32; status [P] int32: 0 solved, 1 a NaN or -inf entry,
+ *   2 infeasible (scipy raises on both; the outputs are filled with -1), 3 a descriptor outside
+ *   cost_len / out_len or a side above 1024 (nothing else is written).
+ * max_cells: the largest rows * cols of the table (a hint: matrices of up to 24576 entries are
+ * staged in LDS).  Static loop bounds, no atomics: ends on any input. */
+int pn_lsa_f32(const float* cost, int64_t cost_len, const int64_t* table, int P, int64_t max_cells,
+               int32_t* row_ind, int32_t* col_ind, int64_t out_len, int32_t* status, void* stream);
+/* The bookkeeping behind the assignments (pairnet_head.py:645-718 and the SeesawLoss label counts of
+ * [3P] seesaw_loss.py's forward) for a batch of B images.  lsa_table / row_ind / col_ind / lsa_status:
+ * pn_lsa_f32's operands with problem 2b = image b's Q x G mask assignment and 2b+1 its R x T triplet
+ * assignment; tgt_table [B][4] int64 = {offset of gt_labels [G], offset of gt_rels [T][3], G, T},
+ * offsets into gt [gt_len] int64.  Writes
+ *   importance [B][Q][Q]: 0, then 1 at (query_of_gt[s], query_of_gt[o]) of every ground-truth
+ *     relation (query_of_gt: the matched query, 1 for an unmatched object as `torch.ones_like`, :648);
+ *   labels [3][B*R] int64: r_labels (gt relation - 1) | sub_ids | obj_ids, -1 for unmatched queries;
+ *   cum_samples [C + 1] += the histogram of the r_labels >= 0 (before pn_seesaw_mean_f32 reads it);
+ *   batch_status [1]: the OR of lsa_status, | 4 for a ground-truth index out of range.  Non-zero:
+ *     the fills only, counts untouched.
+ * G <= 1024, 2 <= Q, R <= 1024, C <= 254. */
+int pn_loss_targets(const int64_t* lsa_table, const int32_t* row_ind, const int32_t* col_ind,
+                    const int32_t* lsa_status, const int64_t* tgt_table, const int64_t* gt,
+                    int64_t gt_len, int B, int Q, int R, int C, float* importance, int64_t* labels,
+                    float* cum_samples, int32_t* batch_status, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * SURVEY 8 f-4, second backward slice (csrc/grad.hip): what the backward of Pair-Net's own tail
  * needs beside the forward kernels above -- the Relation Fusion decoder
  * (pairnet_head.py:353-378; layers: facebook_detr.py:378-432), the Pair Proposal Network
@@ -967,6 +1002,13 @@ int pn_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, const 
                  const float* seg_lr, const float* seg_wd, int nseg, float lr, float beta1,
                  float beta2, float eps, float weight_decay, int step, const float* clip, float pre,
                  void* stream);
+/* pn_adamw_f32 behind a device-side guard (ABI 33): with *guard != 0 -- pn_loss_targets' batch status:
+ * a cost matrix on which `linear_sum_assignment` (matcher.py:262-264) raises in the reference, before
+ * any parameter moves -- nothing is read or written, so p / m / v stay bitwise as they are. */
+int pn_adamw_guarded_f32(float* p, const float* g, float* m, float* v, int64_t n,
+                         const int64_t* seg_off, const float* seg_lr, const float* seg_wd, int nseg,
+                         float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                         const float* clip, float pre, const int32_t* guard, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * fp32 GEMMs on the bf16 matrix pipe from PRE-SPLIT operands (csrc/gemm_s3.hip, round 6)

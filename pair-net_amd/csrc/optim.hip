@@ -57,9 +57,11 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
                                                const float* __restrict__ seg_wd, int nseg,
                                                float lr, float b1, float b2, float eps, float wd,
                                                float bc1, float bc2_sqrt,
-                                               const float* __restrict__ clip, float pre) {
+                                               const float* __restrict__ clip, float pre,
+                                               const int32_t* __restrict__ guard) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
+  if (guard && *guard != 0) return;          // pn_adamw_guarded_f32: p, m, v stay bitwise as they are
   int lo = 0, hi = nseg - 1;                 // the segment with seg_off[s] <= i < seg_off[s + 1]
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -75,11 +77,10 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
   p[i] = pi; m[i] = mi; v[i] = vi;
 }
 
-extern "C" int pn_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n,
-                            const int64_t* seg_off, const float* seg_lr, const float* seg_wd,
-                            int nseg, float lr, float beta1, float beta2, float eps,
-                            float weight_decay, int step, const float* clip, float pre,
-                            void* stream) {
+static int adamw_launch(float* p, const float* g, float* m, float* v, int64_t n,
+                        const int64_t* seg_off, const float* seg_lr, const float* seg_wd, int nseg,
+                        float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                        const float* clip, float pre, const int32_t* guard, void* stream) {
   if (!p || !g || !m || !v || !seg_off || !seg_lr || !seg_wd || n <= 0 || nseg <= 0 || step <= 0)
     return PN_BAD_ARG;
   if (!(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f)) return PN_BAD_ARG;
@@ -87,6 +88,29 @@ extern "C" int pn_adamw_f32(float* p, const float* g, float* m, float* v, int64_
   const float bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
   hipLaunchKernelGGL(k_adamw, dim3(pn_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
                      n, seg_off, seg_lr, seg_wd, nseg, lr, beta1, beta2, eps, weight_decay, bc1,
-                     bc2_sqrt, clip, pre);
+                     bc2_sqrt, clip, pre, guard);
   return PN_LAUNCH_CHECK();
+}
+
+extern "C" int pn_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n,
+                            const int64_t* seg_off, const float* seg_lr, const float* seg_wd,
+                            int nseg, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, int step, const float* clip, float pre,
+                            void* stream) {
+  return adamw_launch(p, g, m, v, n, seg_off, seg_lr, seg_wd, nseg, lr, beta1, beta2, eps,
+                      weight_decay, step, clip, pre, nullptr, stream);
+}
+
+// The same update behind a device-side guard: with *guard != 0 (the batch status of
+// pn_loss_targets: a cost matrix the assignment refuses) every thread returns before it reads or
+// writes a parameter, so a bad batch moves nothing -- without the host looking at the status.
+extern "C" int pn_adamw_guarded_f32(float* p, const float* g, float* m, float* v, int64_t n,
+                                    const int64_t* seg_off, const float* seg_lr,
+                                    const float* seg_wd, int nseg, float lr, float beta1,
+                                    float beta2, float eps, float weight_decay, int step,
+                                    const float* clip, float pre, const int32_t* guard,
+                                    void* stream) {
+  if (!guard) return PN_BAD_ARG;
+  return adamw_launch(p, g, m, v, n, seg_off, seg_lr, seg_wd, nseg, lr, beta1, beta2, eps,
+                      weight_decay, step, clip, pre, guard, stream);
 }

@@ -557,7 +557,10 @@ class PSGTr:
         `SwinBackboneGrad`); False freezes either.  Other keywords go to TailTrainer (lr, lr_mult,
         group, drop_path, train_decoder=False / train_pixel_decoder=False for the frozen-detector
         regimes; `dropout=True` trains with the relation decoder's configured FFN dropout,
-        `seed=` its masks -- nothing of it lives here, the keywords pass through)."""
+        `seed=` its masks; `device_targets=True` builds the loss targets on the device -- Hungarian
+        assignments in HIP, a guarded AdamW launch -- so that `TailTrainer.step` holds no host wait
+        and `train_step` returns `assign_status` beside the losses; nothing of it lives here, the
+        keywords pass through)."""
         from .backbone import ResNet50Hip
         from .train import TailTrainer
         if type(self.bbox_head) is not CrossHead2:

@@ -142,6 +142,10 @@ _SIGS = {
     "pn_grad_norm_clip_f32": (C.c_int, [_vp, _i64, _f32, _f32, _vp, _vp, _vp]),
     "pn_adamw_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32,
                                _f32, _i32, _vp, _f32, _vp]),
+    "pn_adamw_guarded_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _f32, _f32,
+                                       _f32, _f32, _f32, _i32, _vp, _f32, _vp, _vp]),
+    "pn_lsa_f32": (C.c_int, [_vp, _i64, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "pn_loss_targets": (C.c_int, [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32] + [_vp] * 5),
     "pn_msda_loc_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pn_msda_bwd_f32": (C.c_int, [_vp, _i64] + [_vp] * 8 + [_i32, _i32, _i32, _i32, _vp]),
     "pn_gather_probe_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
@@ -209,7 +213,7 @@ _SIGS = {
                                                 _i32, _vp]),
 }
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 32   # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
+ABI_VERSION = 33  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
 
 _lib = None
 
@@ -1500,14 +1504,58 @@ def grad_norm_clip(g, out, scratch, pre=1.0, max_norm=0.0):
 
 
 def adamw(p, g, m, v, seg_off, seg_lr, seg_wd, lr, beta1, beta2, eps, weight_decay, step,
-          clip=None, pre=1.0):
+          clip=None, pre=1.0, guard=None):
+    """`guard`: an int32 device word (`loss_targets`' batch status); non-zero skips the whole
+    update on the device (pn_adamw_guarded_f32)."""
     n = p.numel()
     assert all(t.is_contiguous() and t.numel() == n for t in (p, g, m, v))
     nseg = seg_lr.numel()
     assert seg_off.numel() == nseg + 1 and seg_wd.numel() == nseg
+    if guard is not None:
+        _check(lib().pn_adamw_guarded_f32(_ptr(p), _ptr(g), _ptr(m), _ptr(v), n,
+                                          _ptr(seg_off, torch.int64), _ptr(seg_lr), _ptr(seg_wd),
+                                          nseg, lr, beta1, beta2, eps, weight_decay, step,
+                                          _ptr(clip), pre, _ptr(guard, torch.int32), _stream()),
+               "pn_adamw_guarded_f32")
+        return
     _check(lib().pn_adamw_f32(_ptr(p), _ptr(g), _ptr(m), _ptr(v), n, _ptr(seg_off, torch.int64),
                               _ptr(seg_lr), _ptr(seg_wd), nseg, lr, beta1, beta2, eps, weight_decay,
                               step, _ptr(clip), pre, _stream()), "pn_adamw_f32")
+
+
+LSA_MAX_SIDE = 1024       # the larger side of a pn_lsa_f32 problem (csrc/assign.hip)
+
+
+def lsa(cost, table, row_ind, col_ind, status, max_cells=0):
+    """P = table.shape[0] assignment problems in one launch (`scipy.optimize.linear_sum_assignment`
+    on the device, identical pairs).  cost: flat fp32; table [P][4] int64 on the device = (offset
+    in cost, rows, cols, offset in row_ind / col_ind); row_ind / col_ind int32; status [P] int32
+    (0 ok, 1 NaN / -inf entry, 2 infeasible, 3 descriptor out of range).  `max_cells`: the largest
+    rows * cols, known from shapes on the host (sizes the LDS staging; 0: read from memory)."""
+    assert table.dim() == 2 and table.shape[1] == 4 and table.is_contiguous()
+    P = table.shape[0]
+    assert cost.is_contiguous() and row_ind.numel() == col_ind.numel() and status.numel() >= P
+    _check(lib().pn_lsa_f32(_ptr(cost), cost.numel(), _ptr(table, torch.int64), P, int(max_cells),
+                            _ptr(row_ind, torch.int32), _ptr(col_ind, torch.int32),
+                            row_ind.numel(), _ptr(status, torch.int32), _stream()), "pn_lsa_f32")
+
+
+def loss_targets(lsa_table, row_ind, col_ind, lsa_status, tgt_table, gt, Q, R, importance, labels,
+                 cum_samples, batch_status):
+    """The loss targets of a batch from its 2B assignments (include/pairnet_hip.h): importance
+    [B][Q][Q] fp32, labels [3][B*R] int64 (r_labels | sub_ids | obj_ids), cum_samples [C+1] fp32
+    accumulated in place, batch_status [1] int32."""
+    B = tgt_table.shape[0]
+    assert lsa_table.shape == (2 * B, 4) and tgt_table.shape == (B, 4)
+    assert lsa_table.is_contiguous() and tgt_table.is_contiguous() and gt.is_contiguous()
+    assert importance.numel() == B * Q * Q and labels.numel() == 3 * B * R
+    assert importance.is_contiguous() and labels.is_contiguous() and lsa_status.numel() >= 2 * B
+    _check(lib().pn_loss_targets(_ptr(lsa_table, torch.int64), _ptr(row_ind, torch.int32),
+                                 _ptr(col_ind, torch.int32), _ptr(lsa_status, torch.int32),
+                                 _ptr(tgt_table, torch.int64), _ptr(gt, torch.int64), gt.numel(), B,
+                                 Q, R, cum_samples.numel() - 1, _ptr(importance),
+                                 _ptr(labels, torch.int64), _ptr(cum_samples),
+                                 _ptr(batch_status, torch.int32), _stream()), "pn_loss_targets")
 
 
 def bce_posw_mean(logits, target, out, loss_weight):

@@ -22,6 +22,16 @@ matrices are the only D2H copies; the index bookkeeping of `_get_target_single` 
 a few dozen integers per image) is done on the host from the assignment and uploaded as the
 target vectors.
 
+`loss(..., device_targets=True)` (csrc/assign.hip; off by default) removes those waits: the cost
+kernels of the whole batch run first, ONE `pn_lsa_f32` launch solves the 2B assignments (scipy's
+algorithm on the device, the same pairs, ties included), `pn_loss_targets` does the bookkeeping
+and adds SeesawLoss's label counts into a device-resident copy, and the loss / gradient kernels
+read those device targets.  Ground truth goes up once per batch through pinned memory,
+non-blocking; nothing comes back.  A cost matrix scipy would raise on (NaN / -inf entry,
+infeasible) cannot raise here: it sets `assign_status` (a device word, non-zero) instead, the
+targets are left at their fills and the counts untouched; `TailTrainer` skips the update on it.
+A side above `hip.LSA_MAX_SIDE` (known from shapes) takes the host path.
+
 Reference quirks kept (tests/test_losses_gpu.py): unmatched ground-truth objects point at
 query 1 (`torch.ones_like`, :648); duplicate (subject query, object query) pairs set the
 importance target to 1, not to their count (:660); an image without ground-truth relations
@@ -33,6 +43,13 @@ from scipy.optimize import linear_sum_assignment
 
 from . import hip
 from .config import ConfigDict
+
+
+def _to_dev(t, dev):
+    """Host tensor -> device through pinned memory, non-blocking; a device tensor as it is."""
+    if t.is_cuda:
+        return t if t.device == dev else t.to(dev, non_blocking=True)
+    return t.contiguous().pin_memory().to(dev, non_blocking=True)
 
 
 class CrossHead2Loss:
@@ -83,11 +100,38 @@ class CrossHead2Loss:
             raise NotImplementedError("SeesawLoss over num_relations <= 64 classes")
         # SeesawLoss.cum_samples: the persistent label counts (num_classes + 1 slots, the last
         # one for the objectness dummy the reference appends and never labels)
+        # (default mode: this numpy array; device_targets mode: a device tensor -- the property
+        # below reads either, and the mode may change between calls)
+        self._cum_dev = None
+        self.assign_status = None      # device int32 [1] of the last device_targets call
+        self.last_on_device = False    # whether the last call built its targets on the device
         self.cum_samples = np.zeros(num_relations + 1, dtype=np.float32)
         self.subobj_w = float(so.get("loss_weight", 1.0))
         self.subobj_cw = so.get("class_weight")
         self.match_w = float(im.get("loss_weight", 1.0))
         self._cw = None
+
+    @property
+    def cum_samples(self):
+        """SeesawLoss's counts as a numpy array.  After a `device_targets=True` call they live on
+        the device: reading them here copies them back (a synchronisation) and makes the host
+        array current again, so the next call of either mode continues from the same counts."""
+        if self._cum_dev is not None:
+            self._cum_host = self._cum_dev.cpu().numpy().copy()
+            self._cum_dev = None
+        return self._cum_host
+
+    @cum_samples.setter
+    def cum_samples(self, value):
+        self._cum_host = np.asarray(value, dtype=np.float32)
+        self._cum_dev = None
+
+    def _cum_on(self, dev):
+        """The counts as a device tensor (device_targets mode), uploaded without a wait."""
+        if self._cum_dev is None or self._cum_dev.device != dev:
+            host = torch.from_numpy(self.cum_samples.copy())
+            self._cum_dev = _to_dev(host, dev)
+        return self._cum_dev
 
     def state_dict(self):
         return {"rel_cls_loss.cum_samples": torch.from_numpy(self.cum_samples.copy())}
@@ -144,18 +188,125 @@ class CrossHead2Loss:
                               id_cost=cost2.cpu(), pred_pts=pred_pts, gt_pts=gt_pts))
         return r_labels, sub_ids, obj_ids, importance
 
+    # ---- the same targets without a host wait (csrc/assign.hip) ----
+    def _gt_tensors(self, gt_rels, gt_labels):
+        rels = torch.as_tensor(gt_rels).reshape(-1, 3).to(torch.int64)
+        gl = torch.as_tensor(gt_labels).reshape(-1).to(torch.int64)
+        if rels.shape[0] == 0:
+            raise ValueError("an image without ground-truth relations cannot be a loss target "
+                             "(the reference's CrossHead2.loss fails on it as well)")
+        return rels, gl
+
+    def _fits_device(self, gt_rels_list, gt_labels_list):
+        """Sizes are known from shapes: a side above the solver's limit takes the host path."""
+        sides = [self.Q, self.R]
+        for r, l in zip(gt_rels_list, gt_labels_list):
+            sides += [torch.as_tensor(r).reshape(-1, 3).shape[0], torch.as_tensor(l).numel()]
+        return max(sides) <= hip.LSA_MAX_SIDE and min(sides[2:]) > 0 and self.Q >= 2
+
+    def _targets_device(self, cls, sub, obj, rel, masks, gt_rels_list, gt_labels_list, gt_masks_list,
+                        point_coords, trace):
+        B, dev, Q, R = cls.shape[0], cls.device, self.Q, self.R
+        # ---- sizes and the two tables, on the host from shapes alone ----
+        pieces, lsa_tab, tgt_tab, where = [], [], [], []
+        c_off = o_off = g_off = 0
+        for i in range(B):
+            rels, gl = self._gt_tensors(gt_rels_list[i], gt_labels_list[i])
+            if rels.device != gl.device:
+                rels, gl = _to_dev(rels, dev), _to_dev(gl, dev)
+            T, G = rels.shape[0], gl.shape[0]
+            # (host tensors: an index outside [0, G) raises here as it does on the host path;
+            # device tensors: pn_loss_targets reports it in the status)
+            s_o = rels[:, :2].clamp(0, G - 1) if rels.is_cuda else rels[:, :2]
+            pieces += [gl, rels.reshape(-1), gl[s_o[:, 0]], gl[s_o[:, 1]], rels[:, 2] - 1]
+            where.append(dict(G=G, T=T, gl=g_off, rels=g_off + G, sub=g_off + G + 3 * T,
+                              obj=g_off + G + 4 * T, rel=g_off + G + 5 * T, cost=c_off,
+                              cost2=c_off + Q * G, out=o_off, out2=o_off + min(Q, G)))
+            lsa_tab += [c_off, Q, G, o_off, c_off + Q * G, R, T, o_off + min(Q, G)]
+            tgt_tab += [g_off, g_off + G, G, T]
+            c_off += Q * G + R * T
+            o_off += min(Q, G) + min(R, T)
+            g_off += G + 6 * T
+        head = torch.tensor(lsa_tab + tgt_tab, dtype=torch.int64)
+        nh = head.numel()
+        # ---- ONE pinned, non-blocking upload: tables + ground truth ----
+        if all(not p.is_cuda for p in pieces):
+            buf = torch.empty(nh + g_off, dtype=torch.int64, pin_memory=True)
+            torch.cat([head] + pieces, out=buf)
+            up = buf.to(dev, non_blocking=True)
+            tabs, gt = up[:nh], up[nh:]
+        else:
+            tabs, gt = _to_dev(head, dev), torch.cat([_to_dev(p, dev) for p in pieces])
+        lsa_tab, tgt_tab = tabs[:8 * B].view(2 * B, 4), tabs[8 * B:].view(B, 4)
+        # ---- every cost kernel of the batch, unchanged ----
+        f32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+        cost_all = f32(c_off)
+        kept = []
+        for i, w in enumerate(where):
+            G, T = w["G"], w["T"]
+            pc = None if point_coords is None else point_coords[i]
+            if pc is None:
+                pc = torch.rand((1, self.num_points, 2), device=dev)
+            pts = _to_dev(pc.reshape(-1, 2), dev).to(torch.float32).contiguous()
+            Np = pts.shape[0]
+            pred_pts, gt_pts = f32(Q, Np), f32(G, Np)
+            hip.point_sample(masks[i].contiguous(), pts, pred_pts)
+            gm = _to_dev(torch.as_tensor(gt_masks_list[i]), dev)
+            if gm.dtype not in (torch.bool, torch.uint8):
+                gm = gm.to(torch.float32)
+            hip.point_sample(gm.contiguous(), pts, gt_pts)
+            cost = cost_all[w["cost"]:w["cost"] + Q * G].view(Q, G)
+            hip.mask_match_cost(cls[i].contiguous(), gt[w["gl"]:w["gl"] + G], pred_pts, gt_pts, cost,
+                                self.w_cls, self.w_mask, self.w_dice, self.dice_eps)
+            cost2 = cost_all[w["cost2"]:w["cost2"] + R * T].view(R, T)
+            hip.id_match_cost(sub[i].contiguous(), obj[i].contiguous(), rel[i].contiguous(),
+                              gt[w["sub"]:w["sub"] + T], gt[w["obj"]:w["obj"] + T],
+                              gt[w["rel"]:w["rel"] + T], cost2, *self.id_w)
+            kept.append((pc, cost, cost2, pred_pts, gt_pts))
+        # ---- 2B assignments in one launch, then the bookkeeping ----
+        i32 = lambda n: torch.empty(n, device=dev, dtype=torch.int32)
+        rows, cols, status, bstatus = i32(o_off), i32(o_off), i32(2 * B), i32(1)
+        hip.lsa(cost_all, lsa_tab, rows, cols, status,
+                max_cells=max(max(Q * w["G"], R * w["T"]) for w in where))
+        importance = f32(B, Q, Q)
+        labels = torch.empty(3, B * R, device=dev, dtype=torch.int64)
+        cum = self._cum_on(dev)
+        hip.loss_targets(lsa_tab, rows, cols, status, tgt_tab, gt, Q, R, importance, labels, cum,
+                         bstatus)
+        self.assign_status = bstatus
+        if trace is not None:           # (a debugging aid: this part synchronises)
+            h = lambda t: t.cpu().numpy().astype(np.int64)
+            for w, (pc, cost, cost2, pred_pts, gt_pts) in zip(where, kept):
+                n1, n2 = min(Q, w["G"]), min(R, w["T"])
+                trace.append(dict(point_coords=pc, mask_rows=h(rows[w["out"]:w["out"] + n1]),
+                                  mask_cols=h(cols[w["out"]:w["out"] + n1]),
+                                  triplet_rows=h(rows[w["out2"]:w["out2"] + n2]),
+                                  triplet_cols=h(cols[w["out2"]:w["out2"] + n2]),
+                                  mask_cost=cost.cpu(), id_cost=cost2.cpu(), pred_pts=pred_pts,
+                                  gt_pts=gt_pts))
+        return dict(o=labels[2], s=labels[1], r=labels[0], cum=cum[:self.num_relations],
+                    imp=importance)
+
     # ---- loss / loss_single (pairnet_head.py:419-560) ----
     @torch.no_grad()
     @hip.on_device
     def loss(self, all_cls_scores, all_mask_preds, gt_rels_list, gt_bboxes_list, gt_labels_list,
              gt_masks_list, img_metas, gt_bboxes_ignore=None, point_coords=None, trace=None,
-             grads=None):
+             grads=None, device_targets=False):
         """`point_coords`: optional list of (1, num_points, 2) tensors, one per image (default:
-        `torch.rand` on the device, one draw per image in image order, as the reference)."""
+        `torch.rand` on the device, one draw per image in image order, as the reference).
+        `device_targets`: build the targets on the device without a host wait (module docstring);
+        the same values, `self.assign_status` holds the batch's status word."""
         assert gt_bboxes_ignore is None, "Only supports for gt_bboxes_ignore setting to None."
         cls, sub, obj = all_cls_scores["cls"], all_cls_scores["sub"], all_cls_scores["obj"]
         rel, imp, masks = all_cls_scores["rel"], all_cls_scores["importance"], all_mask_preds["mask"]
         B, dev = cls.shape[0], cls.device
+        self.last_on_device = bool(device_targets) and self._fits_device(gt_rels_list,
+                                                                         gt_labels_list)
+        if self.last_on_device:
+            tgt = self._targets_device(cls, sub, obj, rel, masks, gt_rels_list, gt_labels_list,
+                                       gt_masks_list, point_coords, trace)
+            return self._reduce(obj, sub, rel, imp, tgt.__getitem__, grads)
         r_lab, s_ids, o_ids, gt_imp = [], [], [], []
         for i in range(B):
             out = self._targets_single(sub[i], obj[i], cls[i], masks[i], rel[i], gt_rels_list[i],
@@ -168,6 +319,16 @@ class CrossHead2Loss:
         kept = r_lab[r_lab >= 0]
         np.add.at(self.cum_samples, kept, 1.0)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        host = dict(o=o_ids, s=s_ids, r=r_lab, imp=np.stack(gt_imp, 0))
+        # (uploaded where they are read, launch for launch as before the device mode existed)
+        get = lambda k: up(self.cum_samples[:self.num_relations]) if k == "cum" else up(host[k])
+        return self._reduce(obj, sub, rel, imp, get, grads)
+
+    def _reduce(self, obj, sub, rel, imp, get, grads):
+        """The four reductions and their gradients from the targets `get(name)` hands out as
+        device tensors: "o" / "s" / "r" (int64 [B*R]), "cum" (SeesawLoss's counts including this
+        batch), "imp" ([B][Q][Q])."""
+        dev = obj.device
         out = torch.empty(6, device=dev, dtype=torch.float32)
         if self.subobj_cw is not None and (self._cw is None or self._cw.device != dev):
             self._cw = torch.tensor(self.subobj_cw, dtype=torch.float32, device=dev)
@@ -175,20 +336,19 @@ class CrossHead2Loss:
         if self._cw is not None and self._cw.numel() != nc:
             raise ValueError("subobj_cls_loss.class_weight has %d entries for %d class logits"
                              % (self._cw.numel(), nc))
-        hip.ce_mean(obj.reshape(-1, nc), up(o_ids), self._cw, out[0:1], self.subobj_w)
-        hip.ce_mean(sub.reshape(-1, nc), up(s_ids), self._cw, out[1:2], self.subobj_w)
-        hip.seesaw_mean(rel.reshape(-1, self.num_relations), up(r_lab),
-                        up(self.cum_samples[:self.num_relations]), out[2:3],
+        hip.ce_mean(obj.reshape(-1, nc), get("o"), self._cw, out[0:1], self.subobj_w)
+        hip.ce_mean(sub.reshape(-1, nc), get("s"), self._cw, out[1:2], self.subobj_w)
+        hip.seesaw_mean(rel.reshape(-1, self.num_relations), get("r"), get("cum"), out[2:3],
                         self.seesaw["p"], self.seesaw["q"], self.seesaw["eps"],
                         self.seesaw["loss_weight"])
-        t_imp = up(np.stack(gt_imp, 0))
+        t_imp = get("imp")
         hip.bce_posw_mean(imp.contiguous(), t_imp, out[4:6], self.match_w)
         if grads is not None:
             # SURVEY 8 f-4, first backward slice: d (sum of the four terms) / d their logits, by the
             # analytic derivative kernels beside each reduction (csrc/loss.hip); every term depends
             # on its own logits only.  Filled in place: {"obj", "sub", "rel", "importance"}.
-            t_o, t_s, t_r = up(o_ids), up(s_ids), up(r_lab)
-            cum = up(self.cum_samples[:self.num_relations])
+            t_o, t_s, t_r = get("o"), get("s"), get("r")
+            cum = get("cum")
             g = {k: torch.empty_like(v, memory_format=torch.contiguous_format)
                  for k, v in (("obj", obj), ("sub", sub), ("rel", rel), ("importance", imp))}
             hip.ce_mean_grad(obj.reshape(-1, nc), t_o, self._cw, g["obj"].view(-1, nc), self.subobj_w)

@@ -26,6 +26,19 @@ device -> ONE AdamW launch over the flat parameter buffer that the head's weight
 refresh of the derived weight packs the inference kernels read.  No host synchronisation inside a
 step apart from the reference's own (the Hungarian cost matrices).
 
+`TailTrainer(head, device_targets=True)` removes that one too: the assignments and the target
+bookkeeping run on the device (`head.loss(..., device_targets=True)`, csrc/assign.hip) and `step()`
+contains no host wait at all -- same losses, same parameters, bit for bit.  What the host path
+raises on (a NaN / -inf / infeasible cost matrix, before any parameter moves) the device path
+cannot raise without looking: `step()` returns `assign_status` (a device word) and the AdamW launch
+is the guarded one (`pn_adamw_guarded_f32`), which returns early on a non-zero status, so
+`flat_p` / `flat_m` / `flat_v` stay bitwise unchanged.  The host step counter `steps` still
+advances on such a step (the host does not know), and with it the bias corrections' exponent and
+the dropout draws' key: a skipped batch uses up its step number.  The status word is per rank:
+under `group=` the other ranks do not see it (their all-reduced gradient carries the bad rank's
+NaN), so a data-parallel loop should read `assign_status` and stop, as the host path's exception
+does.
+
 Dropout.  The reference's config has ONE non-zero dropout rate, the Relation Fusion decoder's
 `ffn_drop=0.1` (configs/mask2former/pairnet.py:126): mmcv's FFN drops the hidden rows after the ReLU
 and the FFN's output before the shortcut, twelve `nn.Dropout` per iteration.  It is off by default
@@ -61,13 +74,16 @@ class TailTrainer:
     def __init__(self, head, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  max_norm=0.1, norm_decay_mult=0.0, lr_mult=None, group=None,
                  bucket_bytes=32 << 20, train_decoder=False, train_pixel_decoder=False,
-                 backbone=None, drop_path=False, seed=0, dropout=False):
+                 backbone=None, drop_path=False, seed=0, dropout=False, device_targets=False):
         """`train_decoder`: also train the nine masked decoder layers, `query_feat`, `query_embed`
         and `level_embed` (`HeadGrad`; the reference's `transformer_decoder` group, lr_mult 0.1 by
         default here as in configs/mask2former/pairnet.py:358-363) -- everything of the head behind
         the pixel decoder.  `lr_mult`: {substring of a parameter name: multiplier} (mmcv's
         `paramwise_cfg.custom_keys`)."""
         self.head = head
+        # `device_targets`: loss targets built on the device, a guarded update, no host wait in
+        # `step()` (module docstring); default off: the host assignments, launch for launch
+        self.device_targets = bool(device_targets)
         # `backbone` (a ResNet50Hip): also train its stages 2-4 (`BackboneGrad`; the reference's
         # `backbone` group at lr_mult 0.1, stem / layer1 / BatchNorm frozen as in its config):
         # `step()` then takes the IMAGE tensor.  Its parameters appear as "backbone.<name>".
@@ -344,8 +360,10 @@ class TailTrainer:
     @hip.on_device
     def step(self, feats, img_metas, gt_rels, gt_labels, gt_masks, point_coords=None):
         """One iteration on one batch; returns the four loss terms (device scalars, as
-        `CrossHead2.loss`) plus `grad_norm` (device scalar, before clipping).  `feats`: the four
-        backbone feature maps -- or, for a trainer built with `backbone=`, the image tensor."""
+        `CrossHead2.loss`) plus `grad_norm` (device scalar, before clipping) and, for a
+        `device_targets` trainer, `assign_status` (device int32 scalar; non-zero: the batch's cost
+        matrices were refused and the update was skipped).  `feats`: the four backbone feature
+        maps -- or, for a trainer built with `backbone=`, the image tensor."""
         head, tape = self.head, self.tape
         if head.w is not self._w_dicts[0] or (self.backbone is not None
                                               and self.backbone.w is not self._w_dicts[1]):
@@ -361,10 +379,11 @@ class TailTrainer:
                 feats[3] = self.bb_tape.forward(x4, keep).permute(0, 3, 1, 2)
         outs = head.forward(feats, img_metas)
         up = {}
+        lkw = dict(device_targets=True) if self.device_targets else {}
         drop = self.dropout_descriptor()
         if drop is None:
             losses = head.loss(*outs, gt_rels, None, gt_labels, gt_masks, img_metas,
-                               point_coords=point_coords, grads=up)
+                               point_coords=point_coords, grads=up, **lkw)
         pl = head._last_plan
         masks = outs[1]
         if drop is not None and self.train_decoder and head.exact_mask_order == "full":
@@ -381,7 +400,7 @@ class TailTrainer:
             cls = dict(outs[0])
             cls["rel"] = tape.t["rel"]
             losses = head.loss(cls, masks, gt_rels, None, gt_labels, gt_masks, img_metas,
-                               point_coords=point_coords, grads=up)
+                               point_coords=point_coords, grads=up, **lkw)
         if self.pd_tape is not None:
             self.pd_tape.forward(feats)
         self.reducer.start()
@@ -398,20 +417,31 @@ class TailTrainer:
                 self.bb_tape.backward(dfeats[2], dfeats[1], dfeats[0],
                                       on_ready=lambda e: self.reducer.ready(nh + npd + e))
         self.reducer.finish()
-        self.apply_gradients()
+        # (a call whose sizes exceed the device solver's took the host path, which raises itself)
+        guard = head._loss.assign_status if self.device_targets and head._loss.last_on_device \
+            else None
+        if guard is None:
+            self.apply_gradients()
+        else:
+            self.apply_gradients(guard=guard)
         out = dict(losses)
         out["grad_norm"] = self.clip[0]
+        if self.device_targets:
+            out["assign_status"] = guard[0] if guard is not None else \
+                torch.zeros((), dtype=torch.int32, device=self.dev)
         return out
 
     @torch.no_grad()
     @hip.on_device
-    def apply_gradients(self):
-        """Clip (global L2 norm over the trainable gradients) + AdamW on `tape.flat_grad`."""
+    def apply_gradients(self, guard=None):
+        """Clip (global L2 norm over the trainable gradients) + AdamW on `tape.flat_grad`.
+        `guard`: a device int32 word; non-zero skips the update on the device (`steps` advances
+        all the same)."""
         g = self.flat_grad
         pre = self.reducer.scale
         hip.grad_norm_clip(g, self.clip, self._scratch, pre=pre, max_norm=self.max_norm)
         self.steps += 1
         hip.adamw(self.flat_p, g, self.flat_m, self.flat_v, self.seg_off, self.seg_lr, self.seg_wd,
                   self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.steps,
-                  clip=self.clip, pre=pre)
+                  clip=self.clip, pre=pre, guard=guard)
         self._refresh_derived()

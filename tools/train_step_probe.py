@@ -5,7 +5,9 @@ well (everything behind the frozen backbone), and from the image with the ResNet
 ("all": the reference's whole trainable graph), and where the time goes (HIP events around the
 phases of a step; the Hungarian assignments inside `loss` are host work as in the reference).
 `--dropout [RATE]` builds the trainers with the relation decoder's FFN dropout (no RATE: the config's
-0.1; DESIGN 7b: 24 more latency-sized launches per step), `--scopes tail,head` restricts the scopes.
+0.1; DESIGN 7b: 24 more latency-sized launches per step), `--scopes tail,head` restricts the scopes,
+`--device-targets` builds the trainers with the loss targets on the device (no host wait in a step;
+labnotes/r11.md).
 Prints one JSON line.  `rocprofv3 --kernel-trace --stats -- python tools/train_step_probe.py`
 gives the per-kernel view (profiles/r06_train_step_kernel_stats.csv)."""
 import argparse
@@ -27,9 +29,13 @@ ap.add_argument("steps", nargs="?", type=int, default=10)
 ap.add_argument("--dropout", nargs="?", const=True, default=None,
                 type=lambda v: float(v), help="train with the relation decoder's FFN dropout")
 ap.add_argument("--scopes", default="tail,head,head+pixel_decoder,all")
+ap.add_argument("--device-targets", action="store_true",
+                help="Hungarian assignments and target bookkeeping on the device")
 args = ap.parse_args()
 steps = args.steps
 trainer_kw = {} if args.dropout is None else dict(dropout=args.dropout)
+loss_kw = dict(device_targets=True) if args.device_targets else {}
+trainer_kw.update(loss_kw)
 cfg = pairnet_head_cfg()
 cfg.pop("type")
 head = CrossHead2(**cfg)
@@ -57,11 +63,12 @@ out = {"what": "TailTrainer.step, 800x1333, one image, frozen ResNet-50 features
                "ms per step over %d steps (device wait at both ends) and the phases of one step "
                "(HIP events; `loss` includes the two Hungarian assignments on the host)" % steps}
 out["dropout"] = args.dropout if args.dropout is not None else False
+out["device_targets"] = args.device_targets
 for scope in args.scopes.split(","):
     mode = scope != "tail"
     tr = TailTrainer(head, train_decoder=mode, train_pixel_decoder=scope == "head+pixel_decoder",
                      backbone=net if scope == "all" else None, **trainer_kw)
-    drop = tr.dropout_descriptor() if trainer_kw else None
+    drop = tr.dropout_descriptor() if args.dropout is not None else None
     inp = img if scope == "all" else feats
     for _ in range(3):
         vals = tr.step(inp, metas, gt_rels, gt_labels, gt_masks, point_coords=pts)
@@ -82,7 +89,8 @@ for scope in args.scopes.split(","):
         ev[1].record()
         up = {}
         if drop is None:
-            head.loss(*outs, gt_rels, None, gt_labels, gt_masks, metas, point_coords=pts, grads=up)
+            head.loss(*outs, gt_rels, None, gt_labels, gt_masks, metas, point_coords=pts, grads=up,
+                      **loss_kw)
         ev[2].record()
         pl = head._last_plan
         tape_kw = {} if drop is None else dict(dropout=drop)
@@ -92,7 +100,7 @@ for scope in args.scopes.split(","):
             tr.tape.forward(pl.q, pl.sub_pos, pl.obj_pos, **tape_kw)
         if drop is not None:      # the loss of the DROPPED logits: counted under `taped_forward`
             head.loss(dict(outs[0], rel=tr.tape.t["rel"]), outs[1], gt_rels, None, gt_labels,
-                      gt_masks, metas, point_coords=pts, grads=up)
+                      gt_masks, metas, point_coords=pts, grads=up, **loss_kw)
         if tr.pd_tape is not None:
             tr.pd_tape.forward(feats)
         ev[3].record()
@@ -103,7 +111,7 @@ for scope in args.scopes.split(","):
                 tr.bb_tape.forward(feats[0])
                 tr.bb_tape.backward(dfeats[2], dfeats[1], dfeats[0])
         ev[4].record()
-        tr.apply_gradients()
+        tr.apply_gradients(guard=head._loss.assign_status if args.device_targets else None)
         ev[5].record()
     torch.cuda.synchronize()
     ph = [ev[i].elapsed_time(ev[i + 1]) for i in range(5)]
