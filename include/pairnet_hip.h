@@ -410,6 +410,17 @@ int pn_bilinear_stencil_rows_f32(const float* in, float* out, int B, int hi, int
 /* planar resize + (sigmoid(v) > 0.5  <=>  v > 0) -> uint8 {0,1}  (:834,:842) */
 int pn_bilinear_planar_gt0_u8(const float* in, uint8_t* out, int64_t P, int hi,
                               int wi, int ho, int wo, void* stream);
+/* The subject / object result masks of one image straight from its mask logits
+ * (pairnet_head.py:826-843), without the gathered copies in between:
+ *   masks[r]     = resize(mp[clamp(sub_pos[r])]) > 0,  r < R
+ *   masks[R + r] = resize(mp[clamp(obj_pos[r])]) > 0
+ * mp [Q][hi*wi] fp32; sub_pos / obj_pos int64 [R] on the device, clamped to [0, Q-1] like
+ * pn_gather_rows_f32; masks uint8 [2R][ho][wo].  Bit for bit what pn_gather_rows_f32 followed by
+ * pn_bilinear_planar_gt0_u8 stores; an object that several slots name is resampled once and
+ * stored to each of them.  Q <= 65535, 2R <= 2048.  16-byte stores when wo % 16 == 0 and masks
+ * is 16-byte aligned, 4-byte stores when both are multiples of 4, byte stores otherwise. */
+int pn_pair_masks_u8(const float* mp, const int64_t* sub_pos, const int64_t* obj_pos,
+                     uint8_t* masks, int Q, int R, int hi, int wi, int ho, int wo, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Attention
@@ -559,7 +570,8 @@ int pn_panoptic_f32(const float* masks, const int64_t* labels,
  *   masks [Q][hi][wi] mask logits; labels/scores from pn_cls_argmax_f32 over all_cls
  *   state: pn_panoptic_state_bytes() bytes; its first int32 words, readable after the
  *          stream has drained: nkeep, active, rounds (that dropped something), all_gone
- *   up_scratch Q*ho*wo floats; area_scratch 256 int32; seg [ho*wo] int64 */
+ *   up_scratch Q*ho*wo floats; area_scratch 256 int32; seg [ho*wo] int64
+ *   Q <= 256, 1 <= rounds <= 256, wo <= 2^24 */
 int64_t pn_panoptic_state_bytes(void);
 int pn_panoptic_device_f32(const float* masks, const int64_t* labels, const float* scores,
                            int Q, int num_classes, int hi, int wi, int ho, int wo,
@@ -567,6 +579,14 @@ int pn_panoptic_device_f32(const float* masks, const int64_t* labels, const floa
                            int64_t* seg, int rounds, void* stream);
 int pn_panoptic_continue_f32(void* state, const float* up_scratch, int32_t* area_scratch,
                              int64_t* seg, int ho, int wo, int rounds, void* stream);
+/* The resize step of pn_panoptic_device_f32 on its own: up[j] = resize(masks[kept[j]]) for the
+ * j < nkeep planes `state` lists (nkeep = int32 word 0, kept[256] = int32 words 16..271);
+ * planes j >= nkeep of `up` are not written.  form 1 (what pn_panoptic_device_f32 launches):
+ * workgroups = (strip of output rows, plane) that loop over their strip, so the cost follows
+ * nkeep; form 0: the one-workgroup-per-256-pixels grid of earlier rounds, kept for the
+ * bit-for-bit comparison.  The same expression per pixel in both. */
+int pn_resize_kept_f32(const float* masks, float* up, const void* state, int Q, int hi, int wi,
+                       int ho, int wo, int form, void* stream);
 
 /* One fixed-shape fp32 record per image for the all-gather of predicted triplets that
  * replaces mmdet's pickled collect_results_gpu (tools/test.py:256-267):

@@ -25,6 +25,8 @@ from .head import CrossHead2
 class CrossHeadBaseline(CrossHead2):
     """Drop-in for the reference's `CrossHeadBaseline` (inference half)."""
 
+    _pair_masks_fusable = False      # (CrossHead2.fused_pair_masks: not for this head)
+
     RELATION_ORDER = ("self_attn", "norm", "cross_attn", "norm", "ffn", "norm")
 
     def __init__(self, num_classes, in_channels, num_relations, object_classes=None,

@@ -45,6 +45,8 @@ from .head import CrossHead2, _decoder_param_shapes
 class CrossHeadBBox(CrossHead2):
     """Drop-in for the reference's `CrossHeadBBox` (inference half)."""
 
+    _pair_masks_fusable = False      # (CrossHead2.fused_pair_masks: not for this head)
+
     KEPT = 100          # the literal 100 of pairnet_bbox_head.py:253, :278-279
 
     def __init__(self, num_classes, num_relations, use_mask=False, num_obj_query=100,

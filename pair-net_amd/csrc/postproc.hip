@@ -296,16 +296,12 @@ __global__ __launch_bounds__(256) void k_pan_select(const int64_t* __restrict__ 
 }
 
 // bilinear resize of the kept planes only: out[j] = resize(in[kept[j]]), j < nkeep
-__global__ __launch_bounds__(256) void k_resize_kept(const float* __restrict__ in,
-                                                     float* __restrict__ out,
-                                                     const PanState* __restrict__ st, int hi,
-                                                     int wi, int ho, int wo) {
-  const int j = blockIdx.y;
-  if (j >= st->nkeep) return;
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void resize_kept_pixel(const float* __restrict__ in,
+                                                  float* __restrict__ out,
+                                                  const PanState* __restrict__ st, int j,
+                                                  int64_t e, int oy, int ox, int hi, int wi,
+                                                  int ho, int wo) {
   const int64_t per_plane = (int64_t)ho * wo;
-  if (e >= per_plane) return;
-  const int oy = (int)(e / wo), ox = (int)(e - (int64_t)oy * wo);
   // same index / lambda arithmetic as k_bilinear_planar (resize.hip)
   const float sy = (float)hi / (float)ho, sx = (float)wi / (float)wo;
   float fy = sy * ((float)oy + 0.5f) - 0.5f, fx = sx * ((float)ox + 0.5f) - 0.5f;
@@ -321,6 +317,64 @@ __global__ __launch_bounds__(256) void k_resize_kept(const float* __restrict__ i
   const float v00 = ib[(int64_t)y0 * wi + x0], v01 = ib[(int64_t)y0 * wi + x1];
   const float v10 = ib[(int64_t)y1 * wi + x0], v11 = ib[(int64_t)y1 * wi + x1];
   out[(int64_t)j * per_plane + e] = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
+}
+
+// form 0 (rounds 1-11): one workgroup per 256 pixels of every one of the Q planes; all but
+// nkeep * ceil(ho*wo / 256) of them return at once, and at Q = 100, 384 x 640 dispatching the
+// 96 000 costs more than the resize of the few kept planes
+__global__ __launch_bounds__(256) void k_resize_kept(const float* __restrict__ in,
+                                                     float* __restrict__ out,
+                                                     const PanState* __restrict__ st, int hi,
+                                                     int wi, int ho, int wo) {
+  const int j = blockIdx.y;
+  if (j >= st->nkeep) return;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t per_plane = (int64_t)ho * wo;
+  if (e >= per_plane) return;
+  const int oy = (int)(e / wo), ox = (int)(e - (int64_t)oy * wo);
+  resize_kept_pixel(in, out, st, j, e, oy, ox, hi, wi, ho, wo);
+}
+
+// form 1: workgroup = (strip of `rs` output rows, plane), looping over its strip: Q * ceil(ho / rs)
+// workgroups, the cost follows nkeep.  The same expression per pixel.
+__global__ __launch_bounds__(256) void k_resize_kept_strips(const float* __restrict__ in,
+                                                            float* __restrict__ out,
+                                                            const PanState* __restrict__ st,
+                                                            int hi, int wi, int ho, int wo,
+                                                            int rs) {
+  const int j = blockIdx.y;
+  if (j >= st->nkeep) return;
+  const int y0 = blockIdx.x * rs, y1 = min(y0 + rs, ho);
+  const int n = (y1 - y0) * wo;                  // (rs * wo <= RESIZE_KEPT_STRIP_PIXELS + wo)
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int dy = i / wo, ox = i - dy * wo, oy = y0 + dy;
+    resize_kept_pixel(in, out, st, j, (int64_t)oy * wo + ox, oy, ox, hi, wi, ho, wo);
+  }
+}
+
+#define RESIZE_KEPT_STRIP_PIXELS 4096
+
+static void launch_resize_kept(const float* masks, float* up, const PanState* st, int Q, int hi,
+                               int wi, int ho, int wo, int form, hipStream_t s) {
+  if (form == 0) {
+    hipLaunchKernelGGL(k_resize_kept, dim3(pn_cdiv((int64_t)ho * wo, 256), Q), dim3(256), 0, s,
+                       masks, up, st, hi, wi, ho, wo);
+    return;
+  }
+  int rs = RESIZE_KEPT_STRIP_PIXELS / wo;
+  if (rs < 1) rs = 1;
+  hipLaunchKernelGGL(k_resize_kept_strips, dim3(pn_cdiv(ho, rs), Q), dim3(256), 0, s, masks, up,
+                     st, hi, wi, ho, wo, rs);
+}
+
+extern "C" int pn_resize_kept_f32(const float* masks, float* up, const void* state, int Q, int hi,
+                                  int wi, int ho, int wo, int form, void* stream) {
+  if (!masks || !up || !state || Q <= 0 || Q > 256 || hi <= 0 || wi <= 0 || ho <= 0 || wo <= 0 ||
+      wo > (1 << 24) || form < 0 || form > 1)
+    return PN_BAD_ARG;
+  launch_resize_kept(masks, up, (const PanState*)state, Q, hi, wi, ho, wo, form,
+                     (hipStream_t)stream);
+  return PN_LAUNCH_CHECK();
 }
 
 __global__ __launch_bounds__(256) void k_pan_argmax(const float* __restrict__ up,
@@ -389,7 +443,7 @@ extern "C" int pn_panoptic_device_f32(const float* masks, const int64_t* labels,
   if (!masks || !labels || !scores || !state || !up_scratch || !area_scratch || !seg)
     return PN_BAD_ARG;
   if (Q <= 0 || Q > 256 || rounds < 1 || rounds > 256 || hi <= 0 || wi <= 0 || ho <= 0 ||
-      wo <= 0)
+      wo <= 0 || wo > (1 << 24))
     return PN_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   PanState* st = (PanState*)state;
@@ -397,8 +451,7 @@ extern "C" int pn_panoptic_device_f32(const float* masks, const int64_t* labels,
   (void)hipMemsetAsync(area_scratch, 0, sizeof(int32_t) * 256, s);
   hipLaunchKernelGGL(k_pan_select, dim3(1), dim3(256), 0, s, labels, scores, Q, num_classes - 1,
                      st);
-  hipLaunchKernelGGL(k_resize_kept, dim3(pn_cdiv(HW, 256), Q), dim3(256), 0, s, masks, up_scratch,
-                     st, hi, wi, ho, wo);
+  launch_resize_kept(masks, up_scratch, st, Q, hi, wi, ho, wo, 1, s);
   pan_rounds(st, up_scratch, area_scratch, seg, HW, rounds, s);
   return PN_LAUNCH_CHECK();
 }

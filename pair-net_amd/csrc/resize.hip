@@ -174,6 +174,161 @@ extern "C" int pn_bilinear_planar_gt0_u8(const float* in, uint8_t* out, int64_t 
   return launch_planar(in, out, P, hi, wi, ho, wo, true, stream);
 }
 
+// ---- the subject / object result masks of one image straight from the mask logits
+// (pairnet_head.py:826-843): masks[r] = resize(mp[sub_pos[r]]) > 0, masks[R + r] the same of
+// obj_pos.  The 2R planes are copies of at most Q distinct ones, so a workgroup = (strip of
+// output rows, object q): it collects the output slots that name q (none: it returns), blends
+// and thresholds its strip ONCE and stores it to every such slot.  Nothing is gathered first:
+// the source rows the strip reads are staged in LDS from mp[q] itself.  A thread owns COLS
+// consecutive columns (one 16-, 4- or 1-byte store per slot); their taps are computed once for
+// all rows of the strip, the row tap once per row.  Per pixel the same make_tap / tap_blend on
+// the same four values as k_bilinear_planar4, hence the same bits.
+#define PM_PASSES 2                    // rows of a strip per thread
+#define PM_MAX_SLOTS 2048              // 2R
+#define PM_STAGE_BYTES (48 * 1024)     // source rows of a strip kept in LDS up to this size
+
+template <int COLS, bool STAGE>
+__global__ __launch_bounds__(256) void k_pair_masks(const float* __restrict__ mp,
+                                                    const int64_t* __restrict__ sub_pos,
+                                                    const int64_t* __restrict__ obj_pos,
+                                                    uint8_t* __restrict__ masks, int Q, int R,
+                                                    int hi, int wi, int ho, int wo, int tx_n,
+                                                    int rpp, int cap_rows) {
+  extern __shared__ float pm_rows[];
+  __shared__ uint16_t slot[PM_MAX_SLOTS];
+  __shared__ int wcount[4];
+  const int q = blockIdx.y, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  // the slots that name q, compacted in slot order (ballot + prefix: no atomics)
+  int n = 0;
+  for (int s0 = 0; s0 < 2 * R; s0 += 256) {
+    const int s = s0 + t;
+    bool hit = false;
+    if (s < 2 * R) {
+      int64_t v = s < R ? sub_pos[s] : obj_pos[s - R];
+      if (v < 0) v = 0;                // clamped like k_gather_rows
+      if (v >= Q) v = Q - 1;
+      hit = v == q;
+    }
+    const unsigned long long bal = __ballot(hit);
+    if (lane == 0) wcount[wv] = __popcll(bal);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int c = wcount[w];
+      if (w < wv) before += c;
+      total += c;
+    }
+    if (hit) slot[n + before + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)s;
+    n += total;
+    __syncthreads();
+  }
+  if (n == 0) return;                  // (uniform: nobody asked for this object)
+
+  const int S = rpp * PM_PASSES;
+  const int oy0 = blockIdx.x * S, oy1 = min(oy0 + S, ho);
+  const float* ib = mp + (int64_t)q * hi * wi;
+  int row_lo = 0;
+  if (STAGE) {
+    // make_tap's rows grow with the output row: the strip reads rows row_lo .. row_hi, which
+    // are one contiguous span of mp[q]
+    row_lo = make_tap(oy0, hi, ho).i0;
+    const int row_hi = make_tap(oy1 - 1, hi, ho).i1;
+    // (cap_rows is what the launch sized the LDS for: the host's bound on this span has two
+    // rows to spare, and a store past it cannot happen whatever the bound)
+    const int cnt = min(row_hi - row_lo + 1, cap_rows) * wi;
+    const float* g = ib + (int64_t)row_lo * wi;
+    for (int i = t; i < cnt; i += 256) pm_rows[i] = g[i];
+    __syncthreads();
+  }
+  const int trow = t / tx_n, tcol = t - trow * tx_n;
+  if (trow >= rpp) return;
+  const int cg = wo / COLS;
+  const int64_t plane = (int64_t)ho * wo;
+  for (int c = tcol; c < cg; c += tx_n) {
+    const int ox = c * COLS;
+    Tap tx[COLS];
+#pragma unroll
+    for (int j = 0; j < COLS; ++j) tx[j] = make_tap(ox + j, wi, wo);
+    for (int oy = oy0 + trow; oy < oy1; oy += rpp) {
+      const Tap ty = make_tap(oy, hi, ho);
+      const float *r0, *r1;
+      if (STAGE) {
+        r0 = pm_rows + (ty.i0 - row_lo) * wi;
+        r1 = pm_rows + (ty.i1 - row_lo) * wi;
+      } else {
+        r0 = ib + (int64_t)ty.i0 * wi;
+        r1 = ib + (int64_t)ty.i1 * wi;
+      }
+      uint32_t m[(COLS + 3) / 4];
+#pragma unroll
+      for (int j = 0; j < (COLS + 3) / 4; ++j) m[j] = 0u;
+#pragma unroll
+      for (int j = 0; j < COLS; ++j) {
+        const float v00 = r0[tx[j].i0], v01 = r0[tx[j].i1];
+        const float v10 = r1[tx[j].i0], v11 = r1[tx[j].i1];
+        const float r = tap_blend(ty, tx[j], v00, v01, v10, v11);
+        m[j >> 2] |= (r > 0.f ? 1u : 0u) << (8 * (j & 3));
+      }
+      uint8_t* o = masks + (int64_t)oy * wo + ox;
+      for (int k = 0; k < n; ++k) {
+        uint8_t* p = o + (int64_t)slot[k] * plane;
+        if (COLS == 16) *reinterpret_cast<uint4*>(p) = make_uint4(m[0], m[1], m[2], m[3]);
+        else if (COLS == 4) *reinterpret_cast<uint32_t*>(p) = m[0];
+        else *p = (uint8_t)m[0];
+      }
+    }
+  }
+}
+
+template <int COLS>
+static void launch_pair_masks(bool stage, dim3 grid, size_t lds, hipStream_t s, const float* mp,
+                              const int64_t* sub_pos, const int64_t* obj_pos, uint8_t* masks,
+                              int Q, int R, int hi, int wi, int ho, int wo, int tx_n, int rpp,
+                              int cap_rows) {
+  if (stage)
+    hipLaunchKernelGGL((k_pair_masks<COLS, true>), grid, dim3(256), lds, s, mp, sub_pos, obj_pos,
+                       masks, Q, R, hi, wi, ho, wo, tx_n, rpp, cap_rows);
+  else
+    hipLaunchKernelGGL((k_pair_masks<COLS, false>), grid, dim3(256), 0, s, mp, sub_pos, obj_pos,
+                       masks, Q, R, hi, wi, ho, wo, tx_n, rpp, 0);
+}
+
+extern "C" int pn_pair_masks_u8(const float* mp, const int64_t* sub_pos, const int64_t* obj_pos,
+                                uint8_t* masks, int Q, int R, int hi, int wi, int ho, int wo,
+                                void* stream) {
+  if (!mp || !sub_pos || !obj_pos || !masks || Q <= 0 || Q > 65535 || R <= 0 ||
+      2 * (int64_t)R > PM_MAX_SLOTS || hi <= 0 || wi <= 0 || ho <= 0 || wo <= 0)
+    return PN_BAD_ARG;
+  // 16 columns per thread need whole 16-byte groups in every row of every plane
+  const int cols = ((wo & 15) == 0 && ((uintptr_t)masks & 15) == 0) ? 16
+                   : ((wo & 3) == 0 && ((uintptr_t)masks & 3) == 0) ? 4 : 1;
+  const int cg = wo / cols;
+  const int tx_n = cg < 256 ? cg : 256;          // threads along a row
+  const int rpp = 256 / tx_n;                    // rows per pass of the workgroup
+  const int64_t S = (int64_t)rpp * PM_PASSES;
+  const int64_t rows = S < ho ? S : ho;
+  // source rows under `rows` output rows: at most floor(scale * (rows - 1)) + 3 in exact
+  // arithmetic, one more for the rounding of make_tap's fp32 arithmetic, and two to spare; the
+  // kernel stages no more than this whatever it finds
+  int64_t cap = (int64_t)((double)hi / (double)ho * (double)(rows - 1)) + 6;
+  if (cap > hi) cap = hi;
+  const int64_t lds = cap * wi * (int64_t)sizeof(float);
+  const bool stage = lds <= PM_STAGE_BYTES;
+  dim3 grid(pn_cdiv(ho, S), (unsigned)Q);
+  hipStream_t s = (hipStream_t)stream;
+  if (cols == 16)
+    launch_pair_masks<16>(stage, grid, (size_t)lds, s, mp, sub_pos, obj_pos, masks, Q, R, hi, wi,
+                          ho, wo, tx_n, rpp, (int)cap);
+  else if (cols == 4)
+    launch_pair_masks<4>(stage, grid, (size_t)lds, s, mp, sub_pos, obj_pos, masks, Q, R, hi, wi,
+                         ho, wo, tx_n, rpp, (int)cap);
+  else
+    launch_pair_masks<1>(stage, grid, (size_t)lds, s, mp, sub_pos, obj_pos, masks, Q, R, hi, wi,
+                         ho, wo, tx_n, rpp, (int)cap);
+  return PN_LAUNCH_CHECK();
+}
+
 // ---- the rows a bilinear resize reads: out[b][t][p][:] = in[b][tap t of output pixel p][:],
 // t = 0..3 <-> (i0,j0), (i0,j1), (i1,j0), (i1,j1) of make_tap.  With these rows as the W
 // operand of the mask-logit GEMM, the FULL-RESOLUTION logits a layer's attention mask needs

@@ -205,6 +205,13 @@ class CrossHead2:
         # pass costs 12, and under the pipeline the step is the same (221.1 vs 219.7 images/s,
         # labnotes R6.5): off
         self.msda_s3_out = False
+        # the subject / object result masks of the head's own outputs straight from the mask
+        # logits (pn_pair_masks_u8): stage B no longer gathers MP[sub_pos] / MP[obj_pos] into
+        # sub_seg / obj_seg (107 MB moved per 800 x 1333 image) and get_bboxes resamples every
+        # referenced object once instead of every slot; bit-identical.  forward() still returns
+        # the gathered logits (it issues the two gathers itself); False restores the launches
+        # of rounds 1-11
+        self.fused_pair_masks = True
         self.init_weights()
 
     # ------------------------------------------------------------------ params
@@ -1091,12 +1098,28 @@ class CrossHead2:
         hip.linear(pl.r, w["rel_cls_embed.weight"], w["rel_cls_embed.bias"], pl.rel.view(B * R, -1))
         self._gather_outputs(pl)
 
+    # (the sibling heads select their pairs and build their masks differently: they keep the
+    # gathered logits)
+    _pair_masks_fusable = True
+
+    def _fused_pair_masks(self):
+        # (pn_pair_masks_u8 takes 2R <= 2048, Q <= 65535: the constructor's num_rel_query <= 128,
+        # num_obj_query <= 256 are far inside)
+        return self._pair_masks_fusable and bool(getattr(self, "fused_pair_masks", True))
+
     def _gather_outputs(self, pl):
-        """The subject / object gathers of the selected pairs (pairnet_head.py:380-403)."""
+        """The subject / object gathers of the selected pairs (pairnet_head.py:380-403).  With
+        `fused_pair_masks` the mask logits stay where they are: `_get_bboxes_single` reads
+        MP[sub_pos] / MP[obj_pos] in place, `forward()` gathers them for its caller."""
         B, Q, R = pl.B, self.num_obj_query, self.num_rel_query
         nc = self.num_classes + 1
         hip.gather_rows(pl.cls, pl.sub_pos, pl.sub_cls, B, Q, R, nc)
         hip.gather_rows(pl.cls, pl.obj_pos, pl.obj_cls, B, Q, R, nc)
+        if not self._fused_pair_masks():
+            self._gather_segs(pl)
+
+    def _gather_segs(self, pl):
+        B, Q, R = pl.B, self.num_obj_query, self.num_rel_query
         hip.gather_rows(pl.MP, pl.sub_pos, pl.sub_seg, B, Q, R, pl.HW2)
         hip.gather_rows(pl.MP, pl.obj_pos, pl.obj_seg, B, Q, R, pl.HW2)
 
@@ -1134,6 +1157,7 @@ class CrossHead2:
         cfg = (self.exact_mask_order, self.conv_algo, self.fuse_ppn_front, self.grid_reserve,
                tuple(self.enc_fused_ln), self.group_input_convs,
                getattr(self, "fuse_mask_pack", True), self.gemm_arithmetic, self.msda_s3_out,
+               self._fused_pair_masks(),
                getattr(self, "gather_mask_stencil", True), getattr(self, "fuse_lateral_upadd", False))
         if pl.graph_cfg != cfg:          # a captured graph bakes these switches in
             pl.graph_a = pl.graph_b = None
@@ -1275,14 +1299,25 @@ class CrossHead2:
         """feats: [C2, C3, C4, C5] NCHW fp32 on the GPU; returns the reference's two
         dicts (pairnet_head.py:405-417).  Output tensors are views of per-shape
         buffers that the next forward() of the same shape (and slot) overwrites."""
+        pl = self._forward_plan(feats, img_metas, slot)
+        if self._fused_pair_masks():
+            # stage B left sub_seg / obj_seg alone (post-processing does not read them): the
+            # caller of forward() may, so they are gathered here, outside the stage's graph
+            self._gather_segs(pl)
+        return self._outputs(pl)
+
+    __call__ = forward
+
+    @torch.no_grad()
+    @hip.on_device
+    def _forward_plan(self, feats, img_metas, slot=0):
+        """Both stages on the plan of this shape; returns the plan."""
         B, shapes, hw2 = self._check_feats(feats, img_metas)
         pl = self._plan(B, shapes, hw2, slot, self._feats_nhwc)
         self._run_stage("a", pl, feats)
         self._run_stage("b", pl)
         self._last_plan = pl
-        return self._outputs(pl)
-
-    __call__ = forward
+        return pl
 
     @torch.no_grad()
     @hip.on_device
@@ -1433,18 +1468,22 @@ class CrossHead2:
             mask_preds["mask"][i], cls_scores["cls"][i], cls_scores["sub"][i],
             cls_scores["obj"][i], cls_scores["rel"][i], mask_preds["sub_seg"][i],
             mask_preds["obj_seg"][i], img_metas[i]["img_shape"],
-            img_metas[i]["scale_factor"], rescale, pb=pv[i] if pv is not None else None)
+            img_metas[i]["scale_factor"], rescale, pb=pv[i] if pv is not None else None,
+            own=(pl, i) if pl is not None else None)
             for i in range(len(img_metas)))
         res.panoptic_jobs = tuple(self._pan_jobs)
         return res
 
     def _get_bboxes_single(self, all_masks, all_cls, s_cls, o_cls, r_cls, s_seg, o_seg,
-                           img_shape, scale_factor, rescale=False, pb=None):
+                           img_shape, scale_factor, rescale=False, pb=None, own=None):
         """pairnet_head.py:788-924 on the device, without any host round trip (every
         launch is asynchronous; `panoptic_status()` reads the loop flags back at the
         caller's D2H point).  The outputs are views of buffers owned by the head -- for the
         head's own outputs views of the slot's post-processing arena (`pb`), for foreign
-        inputs one set per (input buffer, output size): the next call overwrites them."""
+        inputs one set per (input buffer, output size): the next call overwrites them.
+        `own` = (plan, image) when the inputs are that plan's outputs: with `fused_pair_masks`
+        the result masks then come from the plan's MP / sub_pos / obj_pos and `s_seg` / `o_seg`
+        are not read."""
         assert len(s_cls) == len(o_cls) == len(r_cls)
         dev = all_cls.device
         R, Q = self.num_rel_query, all_cls.shape[0]
@@ -1474,8 +1513,12 @@ class CrossHead2:
         hip.rel_dists(r_cls, pb["r_dists"], R, self.num_relations)
         # subject / object masks at the original image size (:826-843)
         masks_u8 = pb["masks"]
-        hip.bilinear_planar_gt0(s_seg, masks_u8[:R], R, h, wd, H0, W0)
-        hip.bilinear_planar_gt0(o_seg, masks_u8[R:], R, h, wd, H0, W0)
+        if own is not None and self._fused_pair_masks():
+            pl, i = own
+            hip.pair_masks(pl.MP[i], pl.sub_pos[i], pl.obj_pos[i], masks_u8, Q, R, h, wd, H0, W0)
+        else:
+            hip.bilinear_planar_gt0(s_seg, masks_u8[:R], R, h, wd, H0, W0)
+            hip.bilinear_planar_gt0(o_seg, masks_u8[R:], R, h, wd, H0, W0)
         # panoptic map (:823-825, :845-905), entirely on the device: keep list, stuff-class
         # merging, argmax and the "drop segments of area <= 4 and redo" loop are enqueued as
         # a bounded number of rounds (csrc/postproc.hip); whether the loop has converged is
@@ -1562,8 +1605,12 @@ class CrossHead2:
 
     def simple_test_bboxes(self, feats, img_metas, rescale=False):
         """pairnet_head.py:926-930."""
-        outs = self.forward(feats, img_metas)
-        return self.get_bboxes(*outs, img_metas, rescale=rescale)
+        if not self._fused_pair_masks():
+            return self.get_bboxes(*self.forward(feats, img_metas), img_metas, rescale=rescale)
+        # (the post-processing of the head's own outputs does not read sub_seg / obj_seg: no
+        # gathers of them on this path)
+        pl = self._forward_plan(feats, img_metas)
+        return self.get_bboxes(*self._outputs(pl), img_metas, rescale=rescale)
 
     def simple_test(self, feats, img_metas, rescale=False):
         return self.simple_test_bboxes(feats, img_metas, rescale=rescale)

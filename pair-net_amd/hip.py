@@ -154,6 +154,7 @@ _SIGS = {
     "pn_bilinear_nhwc_f32": (C.c_int, [_vp, _vp] + [_i32] * 7 + [_i64, _i64, _vp]),
     "pn_bilinear_planar_f32": (C.c_int, [_vp, _vp, _i64] + [_i32] * 4 + [_vp]),
     "pn_bilinear_planar_gt0_u8": (C.c_int, [_vp, _vp, _i64] + [_i32] * 4 + [_vp]),
+    "pn_pair_masks_u8": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 6 + [_vp]),
     "pn_mask_pack": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
     "pn_mask_pack_stencil": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "pn_mask_stencil_gemm_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp] +
@@ -181,6 +182,7 @@ _SIGS = {
     "pn_panoptic_device_f32": (C.c_int, [_vp, _vp, _vp] + [_i32] * 6 + [_vp, _vp, _vp, _vp,
                                                                         _i32, _vp]),
     "pn_panoptic_continue_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "pn_resize_kept_f32": (C.c_int, [_vp, _vp, _vp] + [_i32] * 6 + [_vp]),
     "pn_pack_triplets_f32": (C.c_int, [_vp] * 5 + [_i32, _i32, _vp]),
     "pn_copy_stream": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "pn_pack_bool_bits": (C.c_int, [_vp, _vp, _i64, _vp]),
@@ -935,6 +937,13 @@ def topk_strided(scores, elem_stride, row_stride, idx, quot, rem, B, n, div, k):
                                      k, _stream()), "pn_topk_strided_f32")
 
 
+def pair_masks(mp, sub_pos, obj_pos, masks, Q, R, hi, wi, ho, wo):
+    i64 = torch.int64
+    _check(lib().pn_pair_masks_u8(_ptr(mp), _ptr(sub_pos, i64), _ptr(obj_pos, i64),
+                                  _ptr(masks, torch.uint8), Q, R, hi, wi, ho, wo, _stream()),
+           "pn_pair_masks_u8")
+
+
 def gather_rows(x, index, out, B, rows_in, rows_out, length):
     _check(lib().pn_gather_rows_f32(_ptr(x), _ptr(index, torch.int64), _ptr(out), B, rows_in,
                                     rows_out, length, _stream()), "pn_gather_rows_f32")
@@ -995,6 +1004,11 @@ def panoptic_device(masks, labels, scores, Q, num_classes, hi, wi, ho, wo, state
         _ptr(masks), _ptr(labels, torch.int64), _ptr(scores), Q, num_classes, hi, wi, ho, wo,
         _ptr(state, torch.uint8), _ptr(up), _ptr(area, torch.int32), _ptr(seg, torch.int64),
         rounds, _stream()), "pn_panoptic_device_f32")
+
+
+def resize_kept(masks, up, state, Q, hi, wi, ho, wo, form=1):
+    _check(lib().pn_resize_kept_f32(_ptr(masks), _ptr(up), _ptr(state, torch.uint8), Q, hi, wi, ho,
+                                    wo, form, _stream()), "pn_resize_kept_f32")
 
 
 def panoptic_continue(state, up, area, seg, ho, wo, rounds=None):

@@ -28,6 +28,8 @@ from .head import CrossHead2
 class PSGTrHead2(CrossHead2):
     """Drop-in for the reference's `PSGTrHead2` (inference half)."""
 
+    _pair_masks_fusable = False      # (CrossHead2.fused_pair_masks: not for this head)
+
     def __init__(self, num_classes, num_relations, in_channels=(256, 512, 1024, 2048),
                  use_mask=True, num_obj_query=100, num_reg_fcs=2, n_heads=8, embed_dims=256,
                  swin_backbone=None, sync_cls_avg_factor=False, bg_cls_weight=0.02,
