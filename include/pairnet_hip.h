@@ -704,6 +704,34 @@ int pn_triplet_match_boxes(const int32_t* pred_triplets, const int32_t* gt_tripl
                            const int32_t* gt_sub_row, const int32_t* gt_obj_row, float iou_thr,
                            int phrdet, int ignore_rel, uint8_t* match, void* stream);
 
+/* Evaluator feed, part 3 (csrc/evaluate.hip): one image's share of the dataset-level metrics as
+ * integers that stay on the device until the end of the run.
+ * The recall record -- `reduce(np.union1d, pred_to_gt[:k])` of sgg_metrics.py:95-99 fed through
+ * `SGMeanRecall._collect_single` (:741-766) -- from the two uint8 match matrices [R][G] that
+ * the triplet-match entries above write (graph-constrained sgdet, phrase detection):
+ *   gt_predicates [G] int32 in [1, num_rel)      ks [nk] int32, nk <= 8
+ *   num_rel = predicates + background, <= 256
+ *   hits [2][nk][num_rel] int32: hits[mode][j][n] = distinct ground-truth relations with
+ *        predicate n matched by one of the first min(ks[j], R) predictions; slot n = 0 counts
+ *        the relations of every predicate (mode 0 sgdet, 1 phrdet)
+ *   counts [num_rel] int32: ground-truth relations with predicate n; counts[0] = G.
+ * Integer histograms only: the result does not depend on any order of execution. */
+int pn_eval_record(const uint8_t* match_sgdet, const uint8_t* match_phrdet, int R, int G,
+                   const int32_t* gt_predicates, const int32_t* ks, int nk, int num_rel,
+                   int32_t* hits, int32_t* counts, void* stream);
+/* The subject / object IoU statistic, `_compute_iou_panseg` (sgg_metrics.py:1087-1131), from
+ * the integer counts of the mask-IoU entry above: inter [P][n_obj], area_pred [P], area_gt [n_obj];
+ * pred_labels [P] int64, gt_labels [n_obj] int32, gt_sub_row / gt_obj_row [G] the object rows
+ * of the G ground-truth relations.  Per side s (0 subject, 1 object) and relation g:
+ *   valid [2][G] uint8: the class of that object occurs among pred_labels
+ *   best  [2][G] float64: the reference's walk over the predictions of that class in index
+ *        order, best = (best > v) ? best : v from 0, v = (double)inter / (double)(area_pred +
+ *        area_gt - inter), NaN where the union is empty -- Python's max(v, best), NaN included. */
+int pn_eval_iou_best(const int32_t* inter, const int32_t* area_pred, const int32_t* area_gt,
+                     int P, int n_obj, const int64_t* pred_labels, const int32_t* gt_labels,
+                     const int32_t* gt_sub_row, const int32_t* gt_obj_row, int G, uint8_t* valid,
+                     double* best, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Box trunk of the sibling head CrossHeadBBox (pairnet_bbox_head.py:193-359): the
  * input-dependent glue of mmdet's two-stage, box-refining DeformableDetrTransformer

@@ -389,6 +389,10 @@ def multi_gpu_test(detector, dataset, annotations=None, evaluator=None, metrics=
         (`TripletEvaluator`) every rank matches ITS images against their ground truth on its
         own GPU, and only the per-image match lists (a few KB of Python lists) are gathered
         once at the end; rank 0 adds them to `metrics` (`SceneGraphMetrics`) in dataset order.
+        With a `StreamingEvaluator` (any evaluator that has `add` and `state`) the loop calls
+        `evaluator.add(result, ..., index=i)` instead, which reads nothing back; after the last
+        step every rank's `state()` blob (a few KB per image) is gathered, rank 0 merges them
+        and returns `evaluator.summary()`; `metrics` is not needed then.
 
     `dataset[i]` -> `(img, img_metas)` as `simple_test` takes them (one image), or
     `(decoded uint8 (H, W, 3) BGR image, None)`: the detector then runs the reference's test
@@ -417,6 +421,13 @@ def multi_gpu_test(detector, dataset, annotations=None, evaluator=None, metrics=
             hasattr(detector, "_pipelines") and detector._pipelines() and \
             not detector.pipeline_calibrated(depth):
         detector.calibrate_pipeline(*collate([dataset[i] for i in groups[0]]), depth=depth)
+    # an evaluator with `add` and `state` (`StreamingEvaluator`, or a stand-in with the same
+    # two methods) leaves its records on the device: nothing is read back inside the loop
+    streaming = evaluator is not None and hasattr(evaluator, "add") and hasattr(evaluator, "state")
+    if streaming and metrics is not None:
+        import warnings
+        warnings.warn("multi_gpu_test: `metrics` is ignored with a streaming evaluator "
+                      "(its own summary() is the result)")
     local_evals = []
     batches = (collate([dataset[i] for i in grp]) for grp in groups)
     done = 0
@@ -442,6 +453,10 @@ def multi_gpu_test(detector, dataset, annotations=None, evaluator=None, metrics=
             for res, idx, ann in zip(tb.results, grp, anns):
                 if ann is None:
                     continue
+                if streaming:
+                    evaluator.add(res, ann["gt_rels"], ann["gt_labels"], ann["gt_masks"],
+                                  index=idx)
+                    continue
                 ev = evaluator(res, ann["gt_rels"], ann["gt_labels"], ann["gt_masks"])
                 iou = evaluator.iou_stats(res, ann["gt_rels"], ann["gt_labels"],
                                           ann["gt_masks"]) \
@@ -456,7 +471,16 @@ def multi_gpu_test(detector, dataset, annotations=None, evaluator=None, metrics=
         records = torch.zeros((0, col.gatherer.L), dtype=torch.float32)
     out = dict(records=records[:N], num_images=N, world_size=W, rank=rank,
                collectives=col.gatherer.gathered, local_indices=mine)
-    if evaluator is not None:
+    if streaming:
+        blob = evaluator.state()               # (the evaluator's one wait for the GPU)
+        states = [blob]
+        if W > 1:
+            states = [None] * W
+            dist.all_gather_object(states, blob, group=group)
+        if rank == 0:
+            evaluator.merge(states)
+            out["metrics"] = evaluator.summary()
+    elif evaluator is not None:
         evals = [local_evals]
         if W > 1:
             evals = [None] * W

@@ -274,3 +274,311 @@ class SceneGraphMetrics:
         p = rel_pairs[:, 0] * 10000 + rel_pairs[:, 1]
         g = gt_rels[:, 0] * 10000 + gt_rels[:, 1]
         return (p[:, None] == g[None, :]).sum(-1) > 0
+
+
+def host_record(image_eval, gt_rels, num_rel, ks=(20, 50, 100)):
+    """One image's recall record in numpy, from the `pred_to_gt` lists `TripletEvaluator`
+    returned: (hits [2][len(ks)][num_rel], counts [num_rel]) int32 -- what `pn_eval_record`
+    leaves on the device (`reduce(np.union1d, pred_to_gt[:k])`, sgg_metrics.py:95-99, fed
+    through `_collect_single`, :741-766; slot 0 counts every predicate)."""
+    gt_rels = np.asarray(gt_rels).reshape(-1, 3)
+    pred = gt_rels[:, 2].astype(np.int64)
+    hits = np.zeros((2, len(ks), num_rel), np.int32)
+    counts = np.zeros(num_rel, np.int32)
+    np.add.at(counts, pred, 1)
+    counts[0] = gt_rels.shape[0]
+    for m, key in enumerate(("pred_to_gt", "phrdet_pred_to_gt")):
+        for j, k in enumerate(ks):
+            lists = image_eval[key][:k]
+            match = np.unique(np.concatenate([np.asarray(l, np.int64) for l in lists]
+                                             + [np.zeros(0, np.int64)]))
+            np.add.at(hits[m, j], pred[match], 1)
+            hits[m, j, 0] = match.shape[0]
+    return hits, counts
+
+
+class StreamingEvaluator:
+    """`TripletEvaluator` + `SceneGraphMetrics` for a loop that must not wait for the GPU:
+    `add()` enqueues one image's matching on the current stream and leaves a small integer
+    record on the device (`pn_eval_record`: per k and predicate the number of ground-truth
+    relations hit; `pn_eval_iou_best`: the subject / object IoU statistic as float64); nothing
+    is read back before `state()` / `summary()`.  The summary equals
+    `SceneGraphMetrics.summary()` of the host path bit for bit: only integers and IEEE float64
+    quotients come from the device, and the host applies the reference's own float
+    expressions to them in dataset order.
+
+        ev = StreamingEvaluator(num_predicates=56)
+        for each image i:  ev.add(result, gt_rels, gt_labels, gt_masks, index=i)
+        ev.summary()
+
+    Several ranks: `ev.merge(all ranks' ev.state())` on rank 0, then `ev.summary()`.
+    Per-image `pred_to_gt` lists are not produced; `TripletEvaluator` stays for those."""
+
+    _MAGIC = 0x5345                              # first word of a state blob
+
+    def __init__(self, num_predicates, ks=(20, 50, 100), iou_thr=0.5):
+        self.num_predicates = int(num_predicates)
+        self.num_rel = self.num_predicates + 1   # + __background__ (:681-683)
+        self.ks = tuple(int(k) for k in ks)
+        self.iou_thr = float(iou_thr)
+        if not 1 <= len(self.ks) <= 8 or not 2 <= self.num_rel <= 256:
+            raise ValueError("StreamingEvaluator: 1..8 values of k and at most 255 predicates")
+        self._host = {}       # index -> (G, ints [2 nk num_rel + num_rel] int32, sub f64, obj f64)
+        self._skipped = set()
+        self._dev = []        # (index, G, record, valid, best, event): not read back yet
+        self._seen = set()    # every index added so far
+        self._calls = 0
+
+    # ---- ground truth: checked on the host, one pinned buffer, one non-blocking copy ----
+    def _tables(self, gt_rels, gt_labels):
+        if torch.is_tensor(gt_rels) and gt_rels.is_cuda or \
+                torch.is_tensor(gt_labels) and gt_labels.is_cuda:
+            raise ValueError("gt_rels / gt_labels are host data (only the masks live on the device)")
+        rels = np.asarray(gt_rels).reshape(-1, 3).astype(np.int64)
+        lab = np.asarray(gt_labels).reshape(-1).astype(np.int64)
+        G, nobj = rels.shape[0], lab.shape[0]
+        if G and (rels[:, 2].min() < 1 or rels[:, 2].max() >= self.num_rel):
+            raise ValueError("gt_rels: predicate ids must lie in [1, %d)" % self.num_rel)
+        if G and (rels[:, :2].min() < 0 or rels[:, :2].max() >= nobj):
+            raise IndexError("gt_rels: subject / object rows must lie in [0, %d)" % nobj)
+        return rels, lab, G, nobj
+
+    def _upload(self, rels, lab, R, dev, extra=None):
+        """[gt triplets 3G | subject rows G | object rows G | predicates G | labels n_obj |
+        0..max(2R, G) | ks | extra] int32 -> device (the `_to_dev` idiom of losses.py)."""
+        G = rels.shape[0]
+        pieces = [np.stack([lab[rels[:, 0]], rels[:, 2], lab[rels[:, 1]]], 1).reshape(-1),
+                  rels[:, 0], rels[:, 1], rels[:, 2], lab, np.arange(max(2 * R, G)),
+                  np.asarray(self.ks)]
+        pieces = [p.astype(np.int32) for p in pieces] + ([extra] if extra is not None else [])
+        host = torch.from_numpy(np.concatenate(pieces))
+        buf = torch.empty(host.shape[0], dtype=torch.int32, pin_memory=True)
+        buf.copy_(host)
+        up = buf.to(dev, non_blocking=True)
+        out, o = [], 0
+        for p in pieces:
+            out.append(up[o:o + p.shape[0]])
+            o += p.shape[0]
+        return out
+
+    def _index(self, index):
+        idx = self._calls if index is None else int(index)
+        self._calls += 1
+        if idx in self._seen:
+            raise ValueError("StreamingEvaluator: image %d was added before" % idx)
+        self._seen.add(idx)
+        return idx
+
+    def _log(self, idx, G, rec, valid, best):
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(rec.device))
+        self._dev.append((idx, G, rec, valid, best, ev))
+
+    def _record(self, m_s, m_p, R, G, gpred, ks, dev):
+        nk = len(self.ks)
+        rec = torch.empty((2 * nk + 1) * self.num_rel, device=dev, dtype=torch.int32)
+        hip.eval_record(m_s, m_p, R, G, gpred, ks, nk, self.num_rel,
+                        rec[:2 * nk * self.num_rel], rec[2 * nk * self.num_rel:])
+        return rec
+
+    @torch.no_grad()
+    @hip.on_device
+    def add(self, result, gt_rels, gt_labels, gt_masks, index=None, iou=True):
+        """result: the 8-tuple of `get_bboxes` (device tensors); gt_rels (G, 3) / gt_labels
+        (n_obj,) host data; gt_masks (n_obj, H, W) bool, on the device as
+        `dataset.eval_ground_truth` leaves them (host masks go up non-blocking).  Everything is
+        enqueued on the current stream; nothing is read back."""
+        labels, masks, r_dists = result[1], result[3], result[7]
+        dev = masks.device
+        R, C1 = r_dists.shape
+        rels, lab, G, nobj = self._tables(gt_rels, gt_labels)
+        idx = self._index(index)
+        if G == 0:                                # (the reference's loop skips the image)
+            self._skipped.add(idx)
+            return
+        H, W = masks.shape[-2:]
+        gtrip, gs, go, gpred, glab, ar, ks = self._upload(rels, lab, R, dev)
+        gm = _tensor(gt_masks)
+        if not gm.is_cuda:
+            gm = gm.contiguous().pin_memory().to(dev, non_blocking=True)
+        gm = gm.contiguous().view(nobj, H, W)
+        gm = gm.view(torch.uint8) if gm.dtype == torch.bool else gm.to(torch.uint8)
+        pm = masks.contiguous()
+        pm = pm.view(torch.uint8) if pm.dtype == torch.bool else pm.to(torch.uint8)
+        i32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int32)
+        i64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int64)
+        ptrip = i32(R, 3)
+        score = torch.empty(R, device=dev, dtype=torch.float32)
+        hip.pred_triplets(labels, r_dists, ptrip, score, R, C1)
+        # both mask sets packed ONCE; one [2R, n_obj] count matrix for the sgdet match and the
+        # IoU statistic; one union pass and one [R, G] count matrix for phrase detection
+        nw = (H * W + 63) // 64
+        pw, gw = i64(2 * R, nw), i64(nobj, nw)
+        hip.pack_mask_bits(pm, pw, 2 * R, H * W)
+        hip.pack_mask_bits(gm, gw, nobj, H * W)
+        inter, ap, ag = i32(2 * R, nobj), i32(2 * R), i32(nobj)
+        hip.mask_iou_counts(pw, 2 * R, gw, nobj, nw, inter, ap, ag)
+        pu, gu = i64(R, nw), i64(G, nw)
+        hip.mask_or_rows(pw, ar[:R], ar[R:2 * R], pu, R, nw)
+        hip.mask_or_rows(gw, gs, go, gu, G, nw)
+        inter_u, apu, agu = i32(R, G), i32(R), i32(G)
+        hip.mask_iou_counts(pu, R, gu, G, nw, inter_u, apu, agu)
+        m_s = torch.empty(R, G, device=dev, dtype=torch.uint8)
+        m_p = torch.empty(R, G, device=dev, dtype=torch.uint8)
+        hip.triplet_match(ptrip, gtrip, R, G, inter, ap, ag, nobj, ar[:R], ar[R:2 * R], gs, go,
+                          self.iou_thr, False, False, m_s)
+        hip.triplet_match(ptrip, gtrip, R, G, inter_u, apu, agu, G, ar[:R], None, ar[:G], None,
+                          self.iou_thr, True, False, m_p)
+        rec = self._record(m_s, m_p, R, G, gpred, ks, dev)
+        valid = best = None
+        if iou:
+            valid = torch.empty(2 * G, device=dev, dtype=torch.uint8)
+            best = torch.empty(2 * G, device=dev, dtype=torch.float64)
+            hip.eval_iou_best(inter, ap, ag, 2 * R, nobj, labels, glab, gs, go, G, valid, best)
+        self._log(idx, G, rec, valid, best)
+
+    @torch.no_grad()
+    @hip.on_device
+    def add_boxes(self, result, gt_rels, gt_labels, gt_boxes, index=None):
+        """`detection_method="bbox"`: result = the 6-tuple of `CrossHeadBBox.get_bboxes`;
+        gt_boxes (n_obj, 4) xyxy host data.  No IoU statistic (the host path has none)."""
+        det, labels, r_dists = result[0], result[1], result[5]
+        dev = det.device
+        R, C1 = r_dists.shape
+        rels, lab, G, nobj = self._tables(gt_rels, gt_labels)
+        idx = self._index(index)
+        if G == 0:
+            self._skipped.add(idx)
+            return
+        boxes = np.ascontiguousarray(np.asarray(gt_boxes, dtype=np.float32).reshape(nobj, 4))
+        gtrip, gs, go, gpred, glab, ar, ks, gbox = self._upload(
+            rels, lab, R, dev, extra=boxes.reshape(-1).view(np.int32))
+        gbox = gbox.view(torch.float32).view(nobj, 4)       # (the bits of the float32 boxes)
+        ptrip = torch.empty(R, 3, device=dev, dtype=torch.int32)
+        score = torch.empty(R, device=dev, dtype=torch.float32)
+        hip.pred_triplets(labels, r_dists, ptrip, score, R, C1)
+        m = torch.empty(2, R, G, device=dev, dtype=torch.uint8)
+        for ph in (0, 1):
+            hip.triplet_match_boxes(ptrip, gtrip, R, G, det, det.stride(0), gbox, 4, ar[:R],
+                                    ar[R:2 * R], gs, go, self.iou_thr, bool(ph), False, m[ph])
+        self._log(idx, G, self._record(m[0], m[1], R, G, gpred, ks, dev), None, None)
+
+    def add_host(self, index, image_eval, gt_rels, iou=None):
+        """The same record computed in numpy from what `TripletEvaluator.__call__` /
+        `evaluate_boxes` returned (`iou`: optionally its `iou_stats`): the restatement the
+        kernels are tested against, and the entry of loops that run on the host."""
+        rels = np.asarray(gt_rels).reshape(-1, 3)
+        idx = self._index(index)
+        if rels.shape[0] == 0:
+            self._skipped.add(idx)
+            return
+        if rels[:, 2].min() < 1 or rels[:, 2].max() >= self.num_rel:
+            raise ValueError("gt_rels: predicate ids must lie in [1, %d)" % self.num_rel)
+        hits, counts = host_record(image_eval, rels, self.num_rel, self.ks)
+        sub, obj = (np.zeros(0), np.zeros(0)) if iou is None else iou
+        self._host[idx] = (int(rels.shape[0]), np.concatenate([hits.reshape(-1), counts]),
+                           np.asarray(sub, np.float64).reshape(-1),
+                           np.asarray(obj, np.float64).reshape(-1))
+
+    # ---- the one place that waits for the GPU ----
+    def _flush(self):
+        if not self._dev:
+            return
+        dev = self._dev[0][2].device
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            for _, _, rec, valid, best, ev in self._dev:
+                # add() may have run on other streams (the pipeline's chain streams): order
+                # this stream behind each of them, and tell the allocator who reads the blocks
+                cur.wait_event(ev)
+                for t in (rec, valid, best):
+                    if t is not None:
+                        t.record_stream(cur)
+            recs = torch.stack([d[2] for d in self._dev]).cpu().numpy()
+            with_iou = [d for d in self._dev if d[3] is not None]
+            if with_iou:
+                valid = torch.cat([d[3] for d in with_iou]).cpu().numpy().astype(bool)
+                best = torch.cat([d[4] for d in with_iou]).cpu().numpy()
+        o = 0
+        for i, (idx, G, _, v, _, _) in enumerate(self._dev):
+            sub = obj = np.zeros(0)
+            if v is not None:
+                sub = best[o:o + G][valid[o:o + G]]
+                obj = best[o + G:o + 2 * G][valid[o + G:o + 2 * G]]
+                o += 2 * G
+            self._host[idx] = (G, recs[i], sub, obj)
+        self._dev = []
+
+    def records(self):
+        """{index: dict(G, hits [2][nk][num_rel], counts [num_rel], sub_iou, obj_iou)} of the
+        images added so far (waits for the GPU)."""
+        self._flush()
+        n = 2 * len(self.ks) * self.num_rel
+        return {idx: dict(G=G, hits=ints[:n].reshape(2, len(self.ks), self.num_rel),
+                          counts=ints[n:], sub_iou=sub, obj_iou=obj)
+                for idx, (G, ints, sub, obj) in self._host.items()}
+
+    def state(self):
+        """Everything added so far as ONE float64 array (int32 values are exact in it):
+        [magic, images, skipped, nk, num_rel | per image: index, G, n_sub, n_obj, record,
+        sub IoUs, obj IoUs | skipped indices].  The only place the class waits for the GPU;
+        three device-to-host copies however many images there are."""
+        self._flush()
+        parts = [np.array([self._MAGIC, len(self._host), len(self._skipped), len(self.ks),
+                           self.num_rel], np.float64)]
+        for idx in sorted(self._host):
+            G, ints, sub, obj = self._host[idx]
+            parts += [np.array([idx, G, sub.shape[0], obj.shape[0]], np.float64),
+                      ints.astype(np.float64), sub, obj]
+        parts.append(np.array(sorted(self._skipped), np.float64))
+        return np.concatenate(parts)
+
+    def merge(self, states):
+        """Replace this evaluator's contents by the union of `states` (the `state()` blobs of
+        all ranks, its own among them).  An image present in two blobs is an error."""
+        self._flush()
+        host, skipped = {}, set()
+        n = (2 * len(self.ks) + 1) * self.num_rel
+        for blob in states:
+            blob = np.asarray(blob, np.float64)
+            if blob.shape[0] < 5 or int(blob[0]) != self._MAGIC or \
+                    (int(blob[3]), int(blob[4])) != (len(self.ks), self.num_rel):
+                raise ValueError("StreamingEvaluator.merge: not a state of this configuration")
+            o = 5
+            for _ in range(int(blob[1])):
+                idx, G, ns, no = (int(v) for v in blob[o:o + 4])
+                o += 4
+                if idx in host or idx in skipped:
+                    raise ValueError("StreamingEvaluator.merge: image %d occurs twice" % idx)
+                host[idx] = (G, blob[o:o + n].astype(np.int32), blob[o + n:o + n + ns].copy(),
+                             blob[o + n + ns:o + n + ns + no].copy())
+                o += n + ns + no
+            for v in blob[o:o + int(blob[2])]:
+                if int(v) in host or int(v) in skipped:
+                    raise ValueError("StreamingEvaluator.merge: image %d occurs twice" % int(v))
+                skipped.add(int(v))
+        self._host, self._skipped = host, skipped
+        self._seen = set(host) | skipped
+
+    def summary(self):
+        """What `SceneGraphMetrics.summary()` returns after the same images were added to it
+        in dataset order: its lists are rebuilt from the records with the reference's float
+        expressions (`hits / float(G)`, `float(hit / count)`), its own code does the rest."""
+        self._flush()
+        m = SceneGraphMetrics(self.num_predicates, self.ks)
+        nk, nr = len(self.ks), self.num_rel
+        for idx in sorted(self._host):
+            G, ints, sub, obj = self._host[idx]
+            hits, counts = ints[:2 * nk * nr].reshape(2, nk, nr), ints[2 * nk * nr:]
+            m.images += 1
+            for mi, mode in enumerate(("sgdet", "phrdet")):
+                for j, k in enumerate(self.ks):
+                    m.recalls[mode][k].append(int(hits[mi, j, 0]) / float(G))
+                    for n in range(nr):
+                        if counts[n] > 0:
+                            m.collect[mode][k][n].append(
+                                float(int(hits[mi, j, n]) / int(counts[n])))
+            m.sub_iou.extend(sub)
+            m.obj_iou.extend(obj)
+        m.skipped = len(self._skipped)
+        return m.summary()

@@ -193,6 +193,9 @@ _SIGS = {
                                    C.c_double, _i32, _i32, _vp, _vp]),
     "pn_triplet_match_boxes": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp,
                                          _vp, _f32, _i32, _i32, _vp, _vp]),
+    "pn_eval_record": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "pn_eval_iou_best": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
+                                   _vp]),
     "pn_pan_masks_u8": (C.c_int, [_vp] * 5 + [_i32] * 3 + [_vp]),
     "pn_preprocess_u8_f32": (C.c_int, [_vp, _i32, _i32, _vp] + [_i32] * 4 + [C.POINTER(_f32),
                                                                             C.POINTER(_f32), _i32, _vp]),
@@ -1153,6 +1156,27 @@ def triplet_match_boxes(ptrip, gtrip, P, G, pbox, ldp, gbox, ldg, ps, po, gs, go
         _ptr(ptrip, i32), _ptr(gtrip, i32), P, G, _ptr(pbox), ldp, _ptr(gbox), ldg, _ptr(ps, i32),
         _ptr(po, i32), _ptr(gs, i32), _ptr(go, i32), float(thr), int(phrdet), int(ignore_rel),
         _ptr(match, torch.uint8), _stream()), "pn_triplet_match_boxes")
+
+
+def eval_record(match_sgdet, match_phrdet, R, G, gt_pred, ks, nk, num_rel, hits, counts):
+    """hits [2][nk][num_rel], counts [num_rel] int32 from the two match matrices [R][G]."""
+    i32 = torch.int32
+    assert hits.numel() == 2 * nk * num_rel and counts.numel() == num_rel
+    assert match_sgdet.numel() == R * G and match_phrdet.numel() == R * G
+    _check(lib().pn_eval_record(_ptr(match_sgdet, torch.uint8), _ptr(match_phrdet, torch.uint8), R,
+                                G, _ptr(gt_pred, i32), _ptr(ks, i32), nk, num_rel, _ptr(hits, i32),
+                                _ptr(counts, i32), _stream()), "pn_eval_record")
+
+
+def eval_iou_best(inter, area_p, area_g, P, n_obj, pred_labels, gt_labels, gs, go, G, valid, best):
+    """valid [2][G] uint8, best [2][G] float64 from the counts of mask_iou_counts [P][n_obj]."""
+    i32 = torch.int32
+    assert inter.numel() == P * n_obj and pred_labels.numel() >= P and gt_labels.numel() >= n_obj
+    assert valid.numel() == 2 * G and best.numel() == 2 * G
+    _check(lib().pn_eval_iou_best(_ptr(inter, i32), _ptr(area_p, i32), _ptr(area_g, i32), P, n_obj,
+                                  _ptr(pred_labels, torch.int64), _ptr(gt_labels, i32),
+                                  _ptr(gs, i32), _ptr(go, i32), G, _ptr(valid, torch.uint8),
+                                  _ptr(best, torch.float64), _stream()), "pn_eval_iou_best")
 
 
 # ---- box trunk glue (csrc/detr.hip) ----
