@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PN_ABI_VERSION 33
+#define PN_ABI_VERSION 34
 int pn_abi_version(void);
 
 /* ------------------------------------------------------------------------- *
@@ -1045,18 +1045,20 @@ int pn_grad_norm_clip_f32(const float* g, int64_t n, float pre, float max_norm, 
 /* AdamW (torch.optim.AdamW's arithmetic) on p / g / m / v [n] with the effective gradient
  * pre * clip[1] * g (clip: the device pair written by pn_grad_norm_clip_f32, or NULL); segment s
  * covers [seg_off[s], seg_off[s+1]) and uses lr * seg_lr[s], weight_decay * seg_wd[s]; `step`
- * counts from 1 (bias corrections). */
+ * counts from 1 (bias corrections).  The betas are doubles (ABI 34): 1 - beta, 1 - beta^step and
+ * sqrt(1 - beta2^step) are formed in double and rounded to fp32 once, as torch forms the scalars
+ * it applies to fp32 tensors.  0 <= beta < 1, step >= 1, n > 0. */
 int pn_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_off,
-                 const float* seg_lr, const float* seg_wd, int nseg, float lr, float beta1,
-                 float beta2, float eps, float weight_decay, int step, const float* clip, float pre,
+                 const float* seg_lr, const float* seg_wd, int nseg, float lr, double beta1,
+                 double beta2, float eps, float weight_decay, int step, const float* clip, float pre,
                  void* stream);
 /* pn_adamw_f32 behind a device-side guard (ABI 33): with *guard != 0 -- pn_loss_targets' batch status:
  * a cost matrix on which `linear_sum_assignment` (matcher.py:262-264) raises in the reference, before
  * any parameter moves -- nothing is read or written, so p / m / v stay bitwise as they are. */
 int pn_adamw_guarded_f32(float* p, const float* g, float* m, float* v, int64_t n,
                          const int64_t* seg_off, const float* seg_lr, const float* seg_wd, int nseg,
-                         float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                         const float* clip, float pre, const int32_t* guard, void* stream);
+                         float lr, double beta1, double beta2, float eps, float weight_decay,
+                         int step, const float* clip, float pre, const int32_t* guard, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * fp32 GEMMs on the bf16 matrix pipe from PRE-SPLIT operands (csrc/gemm_s3.hip, round 6)

@@ -50,13 +50,18 @@ extern "C" int pn_grad_norm_clip_f32(const float* g, int64_t n, float pre, float
 //   p *= 1 - lr wd;  m += (g - m)(1 - b1);  v = b2 v + (1 - b2) g g;
 //   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
 // with lr = base lr x the segment's lr multiplier, wd = base wd x the segment's decay multiplier.
+// The scalars are torch's: c1 = 1 - b1, c2 = 1 - b2, bc1 and sqrt(bc2) are formed in double on the
+// host from the double betas and rounded once.  Formed in fp32 they are not torch's: 1.f - 0.999f
+// is 1.3e-5 off (float)0.001 and sqrtf(1.f - powf(b2, step)) 6e-6 off in the early steps, about
+// 100 roundings on the update where the rest of the expression has 16
+// (tests/test_loss_optim_kernels_gpu.py bounds m, v and p by those counts; labnotes R14.3).
 __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const float* __restrict__ g,
                                                float* __restrict__ m, float* __restrict__ v,
                                                int64_t n, const int64_t* __restrict__ seg_off,
                                                const float* __restrict__ seg_lr,
                                                const float* __restrict__ seg_wd, int nseg,
-                                               float lr, float b1, float b2, float eps, float wd,
-                                               float bc1, float bc2_sqrt,
+                                               float lr, float c1, float b2, float c2, float eps,
+                                               float wd, float bc1, float bc2_sqrt,
                                                const float* __restrict__ clip, float pre,
                                                const int32_t* __restrict__ guard) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -70,8 +75,8 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
   const float lr_s = lr * seg_lr[lo], wd_s = wd * seg_wd[lo];
   const float gi = g[i] * pre * (clip ? clip[1] : 1.f);
   float pi = p[i] * (1.f - lr_s * wd_s);
-  const float mi = m[i] + (gi - m[i]) * (1.f - b1);
-  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  const float mi = m[i] + (gi - m[i]) * c1;
+  const float vi = b2 * v[i] + c2 * gi * gi;
   const float denom = sqrtf(vi) / bc2_sqrt + eps;
   pi -= (lr_s / bc1) * (mi / denom);
   p[i] = pi; m[i] = mi; v[i] = vi;
@@ -79,22 +84,24 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
 
 static int adamw_launch(float* p, const float* g, float* m, float* v, int64_t n,
                         const int64_t* seg_off, const float* seg_lr, const float* seg_wd, int nseg,
-                        float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                        const float* clip, float pre, const int32_t* guard, void* stream) {
+                        float lr, double beta1, double beta2, float eps, float weight_decay,
+                        int step, const float* clip, float pre, const int32_t* guard,
+                        void* stream) {
   if (!p || !g || !m || !v || !seg_off || !seg_lr || !seg_wd || n <= 0 || nseg <= 0 || step <= 0)
     return PN_BAD_ARG;
-  if (!(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f)) return PN_BAD_ARG;
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
+  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return PN_BAD_ARG;
+  const float c1 = (float)(1.0 - beta1), c2 = (float)(1.0 - beta2);
+  const float bc1 = (float)(1.0 - pow(beta1, (double)step));
+  const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
   hipLaunchKernelGGL(k_adamw, dim3(pn_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     n, seg_off, seg_lr, seg_wd, nseg, lr, beta1, beta2, eps, weight_decay, bc1,
-                     bc2_sqrt, clip, pre, guard);
+                     n, seg_off, seg_lr, seg_wd, nseg, lr, c1, (float)beta2, c2, eps, weight_decay,
+                     bc1, bc2_sqrt, clip, pre, guard);
   return PN_LAUNCH_CHECK();
 }
 
 extern "C" int pn_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n,
                             const int64_t* seg_off, const float* seg_lr, const float* seg_wd,
-                            int nseg, float lr, float beta1, float beta2, float eps,
+                            int nseg, float lr, double beta1, double beta2, float eps,
                             float weight_decay, int step, const float* clip, float pre,
                             void* stream) {
   return adamw_launch(p, g, m, v, n, seg_off, seg_lr, seg_wd, nseg, lr, beta1, beta2, eps,
@@ -106,8 +113,8 @@ extern "C" int pn_adamw_f32(float* p, const float* g, float* m, float* v, int64_
 // writes a parameter, so a bad batch moves nothing -- without the host looking at the status.
 extern "C" int pn_adamw_guarded_f32(float* p, const float* g, float* m, float* v, int64_t n,
                                     const int64_t* seg_off, const float* seg_lr,
-                                    const float* seg_wd, int nseg, float lr, float beta1,
-                                    float beta2, float eps, float weight_decay, int step,
+                                    const float* seg_wd, int nseg, float lr, double beta1,
+                                    double beta2, float eps, float weight_decay, int step,
                                     const float* clip, float pre, const int32_t* guard,
                                     void* stream) {
   if (!guard) return PN_BAD_ARG;

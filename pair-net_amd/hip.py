@@ -140,10 +140,11 @@ _SIGS = {
     "pn_window_attention_bwd_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]
                                     + [_i32] * 7 + [_f32, _vp]),
     "pn_grad_norm_clip_f32": (C.c_int, [_vp, _i64, _f32, _f32, _vp, _vp, _vp]),
-    "pn_adamw_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32,
-                               _f32, _i32, _vp, _f32, _vp]),
-    "pn_adamw_guarded_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _f32, _f32,
-                                       _f32, _f32, _f32, _i32, _vp, _f32, _vp, _vp]),
+    "pn_adamw_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _f32, C.c_double,
+                               C.c_double, _f32, _f32, _i32, _vp, _f32, _vp]),
+    "pn_adamw_guarded_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _f32,
+                                       C.c_double, C.c_double, _f32, _f32, _i32, _vp, _f32, _vp,
+                                       _vp]),
     "pn_lsa_f32": (C.c_int, [_vp, _i64, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
     "pn_loss_targets": (C.c_int, [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32] + [_vp] * 5),
     "pn_msda_loc_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
@@ -218,7 +219,7 @@ _SIGS = {
                                                 _i32, _vp]),
 }
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 33  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
+ABI_VERSION = 34  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
 
 _lib = None
 

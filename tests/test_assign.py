@@ -82,8 +82,9 @@ def test_header_and_binding_declare_the_new_entries():
     declared = set(re.findall(r"\b(pn_[a-z0-9_]+)\s*\(", header))
     for name in ("pn_lsa_f32", "pn_loss_targets", "pn_adamw_guarded_f32"):
         assert name in declared and name in hip._SIGS and name in hip.EXPORTS, name
-    assert int(re.search(r"#define PN_ABI_VERSION (\d+)", header).group(1)) == hip.ABI_VERSION == 33
-    # the existing optimizer entry keeps its signature; the guarded one adds the status word
+    assert int(re.search(r"#define PN_ABI_VERSION (\d+)", header).group(1)) == hip.ABI_VERSION == 34
+    # the existing optimizer entry keeps its argument list (the betas are doubles from ABI 34); the
+    # guarded one adds the status word
     assert len(hip._SIGS["pn_adamw_f32"][1]) == 18 and len(hip._SIGS["pn_adamw_guarded_f32"][1]) == 19
     assert callable(hip.lsa) and callable(hip.loss_targets) and "assign" in B.SOURCES
     for cite in ("matcher.py:262-264", "mask_hungarian_assigner.py", "pairnet_head.py:645-718"):
