@@ -1115,6 +1115,87 @@ typedef struct pn_gemm_s3_desc {
 #define PN_GEMM_S3_TILE192 2  /* force the 192 x 256 tile (N >= 512, plain epilogue) whatever its tile count */
 int pn_gemm_s3_f32(const pn_gemm_s3_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * The Mask2Former segmentation losses (csrc/seg_loss.hip; pair-net_amd/seg_losses.py drives them):
+ * per-decoder-layer loss_cls / loss_mask / loss_dice with Hungarian matching per (layer, image),
+ * importance-sampled mask points and deep supervision, values and d loss / d logits -- the
+ * reference's panoptic_heads/mask2former_head.py:157-324 with maskformer_head.py:181-240,305-354
+ * (again in relation_heads/baseline.py:588-653) under configs/mask2former/baseline_r50_psg.py:351-389.
+ * The matching itself is pn_point_sample_f32 + pn_mask_match_cost_f32 + ONE pn_lsa_f32 launch over
+ * the L * B problems.  Fixed-order reductions, no floating-point atomics: bitwise reproducible.
+ * Entries added at ABI 34 (adding entries is compatible).
+ * ------------------------------------------------------------------------- */
+/* The `torch.rand` draws of mask2former_head.py:191 and point_sample.py:61,84-86 as a pure function
+ * of their arguments: out[s][i] = (word >> 8) * 2^-24 in [0, 1), word = output word i % 4 of
+ * Philox4x32-10 at counter (i / 4, rank, site + s * site_stride, step), key (seed & 0xffffffff,
+ * seed >> 32) -- csrc/dropout.hip's scheme.  out [nsites][n]; 0 < n <= 2^34, 0 < nsites <= 65535. */
+int pn_uniform_f32(float* out, int64_t n, int nsites, uint32_t site_stride, uint64_t seed,
+                   uint32_t rank, uint32_t step, uint32_t site, void* stream);
+/* `_get_target_single`'s bookkeeping (mask2former_head.py:205-221 with MaskPseudoSampler) for the
+ * P = L * B problems of one pn_lsa_f32 launch.  table [P][6] int64 on the device, problem p = l * B + b:
+ * {index of the problem in lsa_status, or -1 for an image without ground truth; offset of its
+ * entries in row_ind / col_ind; their number n = min(Q, G); offset of the image's labels in
+ * gt_labels; G; offset of its n rows in `matched`}.  Writes
+ *   labels [L][B * Q] int64: the matched ground truth's class, num_classes = C for the rest;
+ *   matched [Mtot][4] int64: (layer, image, query, index into gt_labels / the concatenated
+ *     ground-truth masks) ordered by (layer, image, query ascending) -- the order of
+ *     `mask_preds[mask_weights > 0]` and of the concatenated `mask_targets` (:263,283);
+ *   mcount [L] int32: assigned rows per layer;  status [1] int32: the OR of the problems'
+ *     lsa_status, | 4 for an index or label out of range, | 8 for a table row out of range.
+ * A problem with a non-zero status keeps its fills (labels C, matched rows -1).  L <= 64. */
+int pn_seg_targets(const int64_t* table, const int32_t* row_ind, const int32_t* col_ind,
+                   const int32_t* lsa_status, int nlsa, const int64_t* gt_labels, int64_t gt_len,
+                   int64_t out_len, int L, int B, int Q, int C, int64_t Mtot, int64_t* labels,
+                   int64_t* matched, int32_t* mcount, int32_t* status, void* stream);
+/* get_uncertain_point_coords_with_randomness (panoptic_heads/point_sample.py:32-88) for the M
+ * matched masks, one workgroup each: row m samples map (l * B + b) * Q + q of maps [nmaps][h][w]
+ * (its `matched` row) at cand [M][S][2], keeps the k candidates with the smallest |logit| (what
+ * `torch.topk(-|x|, k)` keeps; exact, ties to the lower candidate index) and writes them in
+ * ascending candidate order, followed by tail [M][Np - k][2], to pts [M][Np][2].  keys [M][S]
+ * uint32: the sampled |logit| bit patterns (scratch of the four-pass radix select; readable
+ * afterwards).  A row with layer < 0: zeros.  0 <= k <= Np, k <= S; tail may be NULL iff k == Np. */
+int pn_uncertain_points_f32(const float* maps, int64_t nmaps, const int64_t* matched, int64_t M,
+                            int B, int Q, int h, int w, const float* cand, const float* tail, int S,
+                            int k, int Np, uint32_t* keys, float* pts, void* stream);
+/* [3P] mmcv point_sample with a point set PER ROW (mask2former_head.py:300-306): out[m][i] = map
+ * idx[m] of maps [nmaps][h][w] (fp32, or uint8 0/1) sampled at pts[m][i] with pn_point_sample_f32's
+ * arithmetic (bilinear, zeros padding, align_corners=False); idx[m] outside [0, nmaps): zeros.
+ * M <= 65535. */
+int pn_point_sample_rows_f32(const void* maps, int maps_are_u8, int64_t nmaps, const int64_t* idx,
+                             const float* pts, float* out, int64_t M, int h, int w, int Np,
+                             void* stream);
+/* loss_mask ([3P] sigmoid CrossEntropyLoss) and loss_dice ([3P] DiceLoss: use_sigmoid, activate,
+ * naive_dice) of L layers over x / t [M][Np], M = L * Ml rows in `matched` order
+ * (mask2former_head.py:308-322), s = sigmoid(x):
+ *   sums [M][4] = { sum_p BCE(x, t), a = sum_p s t, b = sum_p s, c = sum_p t }
+ *   out[l]     = w_mask * sum_m sums[m][0] / (N_l * Np + eps32)
+ *   out[L + l] = w_dice * sum_m (1 - (2 a + dice_eps) / (b + c + dice_eps)) / (N_l + eps32)
+ *   out[2L + l], out[3L + l]: the two denominators
+ * N_l = num_total_masks when > 0, else max(assigned rows of layer l, 1) (:278-279); rows with layer
+ * < 0 are skipped.  coef [M][Np] (or NULL) = d (out[l] + out[L + l]) / d x[m][p]. */
+int pn_mask_point_loss_f32(const float* x, const float* t, const int64_t* matched, int64_t M, int Np,
+                           int L, int Ml, float w_mask, float w_dice, float dice_eps,
+                           float num_total_masks, float* sums, float* out /* [4L] */, float* coef,
+                           void* stream);
+/* The transpose of the bilinear sample (the backward of mask2former_head.py:304): grad [M][h][w] =
+ * sum over row m's points of coef[m][p] * the tap weight, taps outside the map dropped.  No
+ * floating-point atomics: per mask, a stable counting sort of the points by the pixel of their
+ * top-left tap, then every pixel sums its up-to-four bins in that order.  scratch:
+ * pn_point_scatter_scratch_ints(M, Np, h, w) int32. */
+int64_t pn_point_scatter_scratch_ints(int64_t M, int Np, int h, int w);
+int pn_point_scatter_grad_f32(const float* coef, const float* pts, float* grad, int32_t* scratch,
+                              int64_t M, int Np, int h, int w, void* stream);
+/* loss_cls of L layers (mask2former_head.py:273-276; [3P] mmdet CrossEntropyLoss with class weights,
+ * avg_factor = class_weight[labels].sum(), weight_reduce_loss's eps32):
+ *   out[l] = loss_weight * sum_r cw[y] (lse(x_r) - x_r[y]) / (sum_r cw[y] + eps32)
+ *   grad[l][r][c] = loss_weight * cw[y] / (sum_r cw[y] + eps32) * (softmax(x_r)[c] - [c == y])
+ * logits / grad [L][rows][C] contiguous, target [L][rows] in [0, C), class_weight [C];
+ * rows <= 4096; one workgroup per layer, rows summed in row order. */
+int pn_ce_avg_f32(const float* logits, const int64_t* target, const float* class_weight, float* out,
+                  int L, int rows, int C, float loss_weight, void* stream);
+int pn_ce_avg_grad_f32(const float* logits, const int64_t* target, const float* class_weight,
+                       float* grad, int L, int rows, int C, float loss_weight, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ from .pipeline import PipelinedHead  # noqa: F401
 from .grad import (BackboneGrad, FfnDropout, HeadGrad, PixelDecoderGrad,  # noqa: F401
                    RelationTailGrad, SwinBackboneGrad)
 from .train import TailTrainer  # noqa: F401
+from .seg_losses import Mask2FormerLoss  # noqa: F401
 from .preprocess import TestPipeline  # noqa: F401
 from .train_pipeline import AugParams, HalfSizeMasks, TrainPipeline  # noqa: F401
 from .detector import (PSGTr, Result, ResultStreamer, build_detector, load_checkpoint,  # noqa: F401
@@ -29,4 +30,4 @@ __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "Cros
            "SwinTransformerHip", "pairnet_swin", "swin_backbone_cfg", "TestPipeline", "test_pipeline_cfg",
            "CrossHeadBBox", "ChannelMapper", "bbox_head_cfg", "channel_mapper_cfg", "cross_r101_vg",
            "TripletEvaluator", "SceneGraphMetrics", "StreamingEvaluator", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "TailTrainer", "FfnDropout",
-           "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg"]
+           "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg", "Mask2FormerLoss"]

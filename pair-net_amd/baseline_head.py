@@ -36,6 +36,10 @@ class CrossHeadBaseline(CrossHead2):
             raise AssertionError("num_obj_query must equal num_rel_query")
         self.object_classes, self.predicate_classes = object_classes, predicate_classes
         self.return_all_layers = False
+        # the Mask2Former loss options of baseline_r50_psg.py:351-389 (`seg_losses`)
+        self._seg_loss_cfg = dict(train_cfg=kwargs.get("train_cfg"), loss_cls=kwargs.get("loss_cls"),
+                                  loss_mask=kwargs.get("loss_mask"), loss_dice=kwargs.get("loss_dice"))
+        self._seg_loss = None
         super().__init__(num_classes, in_channels, num_relations, num_obj_query=num_obj_query,
                          num_rel_query=num_rel_query, use_mask=use_mask, **kwargs)
 
@@ -139,6 +143,25 @@ class CrossHeadBaseline(CrossHead2):
                      subject_scores=pl.sub_scores, object_scores=pl.obj_scores),
                 dict(mask=pl.MP_all.view(n, B, Q, H2, W2), sub_seg=pl.sub_seg.view(B, R, H2, W2),
                      obj_seg=pl.obj_seg.view(B, R, H2, W2)))
+
+    # ------------------------------------------------------- segmentation losses
+    def seg_losses(self, all_cls_scores, all_mask_preds, gt_labels_list, gt_masks_list, img_metas,
+                   **kw):
+        """The Mask2Former part of the reference's `loss` (baseline.py:588-653, i.e.
+        panoptic_heads/mask2former_head.py:223-324 per decoder layer): {loss_cls, loss_mask,
+        loss_dice, d0.loss_cls, ...} from the two dicts a `return_all_layers=True` forward returns
+        (seg_losses.py; `grads={}` adds d sum / d logits, `points=` / `seed=` / `step=` fix the
+        draws).  The relation terms of the full `loss` (:655-694, 828-907) are not built."""
+        if self._seg_loss is None:
+            from .seg_losses import Mask2FormerLoss
+            cfg = dict(self._seg_loss_cfg)
+            tc = cfg.pop("train_cfg")
+            if tc is not None:      # (the id assigner belongs to the relation terms)
+                tc = {k: v for k, v in dict(tc).items() if k != "id_assigner"}
+            self._seg_loss = Mask2FormerLoss(self.num_classes, self.num_obj_query, train_cfg=tc,
+                                             **cfg)
+        return self._seg_loss.loss(all_cls_scores["cls"], all_mask_preds["mask"], gt_labels_list,
+                                   gt_masks_list, img_metas, **kw)
 
     # ------------------------------------------------------- post-processing
     @torch.no_grad()

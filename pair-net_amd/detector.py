@@ -511,6 +511,27 @@ class PSGTr:
         return self.bbox_head.val_losses(x, img_metas, gt_rels, gt_bboxes, gt_labels, gt_masks,
                                          gt_bboxes_ignore, **kw)
 
+    @torch.no_grad()
+    def val_seg_losses(self, img, img_metas, gt_labels, gt_masks, **kw):
+        """The Mask2Former segmentation losses of a head that has them (`CrossHeadBaseline.seg_losses`:
+        per-decoder-layer loss_cls / loss_mask / loss_dice, relation_heads/baseline.py:588-653) as
+        validation values: extract_feat -> ground-truth masks prepared as in `forward_train`
+        (psgtr.py:126-141) -> head forward with all decoder layers -> `seg_losses`.  Keywords go to
+        `Mask2FormerLoss.loss` (`grads={}`, `points=`, `seed=`, `step=`, `num_total_masks=`)."""
+        head = self.bbox_head
+        if not hasattr(head, "seg_losses"):
+            raise NotImplementedError("%s has no segmentation losses here (CrossHeadBaseline does)"
+                                      % type(head).__name__)
+        x = self.extract_feat(img)
+        gt_masks = self._prepare_gt_masks(img, gt_masks)
+        old = head.return_all_layers
+        head.return_all_layers = True
+        try:
+            outs = head.forward(x, img_metas)
+        finally:
+            head.return_all_layers = old
+        return head.seg_losses(*outs, gt_labels, gt_masks, img_metas, **kw)
+
     def _prepare_gt_masks(self, img, gt_masks):
         """PSGTr.forward_train's ground-truth mask preparation (psgtr.py:126-141): zero-pad to the
         batch tensor's (H, W), nearest-resize to (H // 2, W // 2); one kernel per image."""

@@ -217,6 +217,20 @@ _SIGS = {
     "pn_query_score_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "pn_box_triplets_f32": (C.c_int, [_vp] * 5 + [_vp, _i32, _i32, _f32, _f32, C.POINTER(_f32),
                                                 _i32, _vp]),
+    "pn_uniform_f32": (C.c_int, [_vp, _i64, _i32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
+                                 C.c_uint32, _vp]),
+    "pn_seg_targets": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _i32,
+                                 _i64, _vp, _vp, _vp, _vp, _vp]),
+    "pn_uncertain_points_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp,
+                                          _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pn_point_sample_rows_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32,
+                                           _vp]),
+    "pn_mask_point_loss_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _f32, _f32,
+                                         _f32, _vp, _vp, _vp, _vp]),
+    "pn_point_scatter_scratch_ints": (_i64, [_i64, _i32, _i32, _i32]),
+    "pn_point_scatter_grad_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "pn_ce_avg_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
+    "pn_ce_avg_grad_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 34  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
@@ -1600,3 +1614,109 @@ def loss_targets(lsa_table, row_ind, col_ind, lsa_status, tgt_table, gt, Q, R, i
 def bce_posw_mean(logits, target, out, loss_weight):
     _check(lib().pn_bce_posw_mean_f32(_ptr(logits), _ptr(target), _ptr(out), logits.numel(),
                                       loss_weight, _stream()), "pn_bce_posw_mean_f32")
+
+
+# ---- the Mask2Former segmentation losses (csrc/seg_loss.hip; composed in seg_losses.py) ----------
+SEG_SITE_ASSIGN, SEG_SITE_CANDIDATES, SEG_SITE_TAIL = 0, 1, 2   # site = 4 * layer + purpose
+
+
+def uniform(out, seed, rank, step, site, site_stride=0):
+    """out [nsites][n] (or [n]) <- Philox4x32-10 uniforms in [0, 1): element i of row s is word i % 4
+    at counter (i / 4, rank, site + s * site_stride, step) under key `seed`, times 2^-24 after
+    dropping its low 8 bits.  Nothing is uploaded; the same arguments give the same bits."""
+    assert out.is_contiguous() and out.dim() in (1, 2)
+    nsites = out.shape[0] if out.dim() == 2 else 1
+    _check(lib().pn_uniform_f32(_ptr(out), out.shape[-1], nsites, site_stride, seed, rank, step,
+                                site, _stream()), "pn_uniform_f32")
+
+
+def seg_targets(table, row_ind, col_ind, lsa_status, gt_labels, L, B, Q, C, labels, matched, mcount,
+                status):
+    """include/pairnet_hip.h: labels [L][B*Q], matched [Mtot][4], mcount [L], status [1] from the
+    L * B assignments (table [L*B][6] int64)."""
+    assert table.shape == (L * B, 6) and table.is_contiguous() and labels.numel() == L * B * Q
+    assert labels.is_contiguous() and matched.is_contiguous() and mcount.numel() >= L
+    Mtot = matched.shape[0]
+    assert matched.dim() == 2 and matched.shape[1] == 4 and row_ind.numel() == col_ind.numel()
+    _check(lib().pn_seg_targets(_ptr(table, torch.int64), _ptr(row_ind, torch.int32),
+                                _ptr(col_ind, torch.int32), _ptr(lsa_status, torch.int32),
+                                lsa_status.numel(), _ptr(gt_labels, torch.int64), gt_labels.numel(),
+                                row_ind.numel(), L, B, Q, C, Mtot, _ptr(labels, torch.int64),
+                                _ptr(matched, torch.int64) if Mtot else None,
+                                _ptr(mcount, torch.int32), _ptr(status, torch.int32), _stream()),
+           "pn_seg_targets")
+
+
+def uncertain_points(maps, matched, B, Q, cand, tail, k, keys, pts):
+    """maps [nmaps][h][w] fp32, matched [M][4], cand [M][S][2], tail [M][Np-k][2] or None, keys
+    [M][S] int32 (bit patterns of the sampled |logit|), pts [M][Np][2]."""
+    nmaps, h, w = maps.shape
+    M, S, _ = cand.shape
+    Np = pts.shape[1]
+    assert maps.is_contiguous() and matched.is_contiguous() and cand.is_contiguous() and \
+        pts.is_contiguous() and keys.is_contiguous() and matched.shape == (M, 4)
+    assert pts.shape == (M, Np, 2) and keys.shape == (M, S)
+    assert tail is None or (tail.is_contiguous() and tail.shape == (M, Np - k, 2))
+    _check(lib().pn_uncertain_points_f32(_ptr(maps), nmaps, _ptr(matched, torch.int64), M, B, Q, h, w,
+                                         _ptr(cand), _ptr(tail), S, k, Np, _ptr(keys, torch.int32),
+                                         _ptr(pts), _stream()), "pn_uncertain_points_f32")
+
+
+def point_sample_rows(maps, idx, pts, out):
+    """out[m][i] = map idx[m] of maps [nmaps][h][w] (fp32 or bool / uint8) at pts[m][i]."""
+    nmaps, h, w = maps.shape
+    M, Np, _ = pts.shape
+    u8 = maps.dtype in (torch.bool, torch.uint8)
+    assert maps.is_contiguous() and pts.is_contiguous() and out.is_contiguous()
+    assert idx.numel() == M and out.shape == (M, Np)
+    _check(lib().pn_point_sample_rows_f32(_ptr(maps, maps.dtype), int(u8), nmaps,
+                                          _ptr(idx, torch.int64), _ptr(pts), _ptr(out), M, h, w, Np,
+                                          _stream()), "pn_point_sample_rows_f32")
+
+
+def mask_point_loss(x, t, matched, L, w_mask, w_dice, dice_eps, sums, out, coef=None,
+                    num_total_masks=0.0):
+    """x / t [M][Np], M = L * Ml; sums [M][4]; out [4L] = loss_mask | loss_dice | denominators; coef
+    [M][Np] or None."""
+    M, Np = x.shape
+    assert M % L == 0 and t.shape == x.shape and x.is_contiguous() and t.is_contiguous()
+    assert sums.numel() == 4 * M and out.numel() == 4 * L and matched.shape == (M, 4)
+    assert coef is None or (coef.shape == x.shape and coef.is_contiguous())
+    _check(lib().pn_mask_point_loss_f32(_ptr(x), _ptr(t), _ptr(matched, torch.int64), M, Np, L,
+                                        M // L, w_mask, w_dice, dice_eps, num_total_masks,
+                                        _ptr(sums), _ptr(out), _ptr(coef), _stream()),
+           "pn_mask_point_loss_f32")
+
+
+def point_scatter_scratch_ints(M, Np, h, w):
+    return lib().pn_point_scatter_scratch_ints(M, Np, h, w)
+
+
+def point_scatter_grad(coef, pts, grad, scratch):
+    """grad [M][h][w] <- the transpose of the bilinear sample of coef [M][Np] at pts [M][Np][2]."""
+    M, Np = coef.shape
+    _, h, w = grad.shape
+    assert coef.is_contiguous() and pts.is_contiguous() and grad.is_contiguous()
+    assert pts.shape == (M, Np, 2) and grad.shape[0] == M
+    assert scratch.numel() >= point_scatter_scratch_ints(M, Np, h, w)
+    _check(lib().pn_point_scatter_grad_f32(_ptr(coef), _ptr(pts), _ptr(grad),
+                                           _ptr(scratch, torch.int32), M, Np, h, w, _stream()),
+           "pn_point_scatter_grad_f32")
+
+
+def ce_avg(logits, target, class_weight, out, loss_weight):
+    """logits [L][rows][C], target [L][rows] in [0, C), class_weight [C], out [L]."""
+    L, rows, Cc = logits.shape
+    assert logits.is_contiguous() and target.is_contiguous() and target.numel() == L * rows
+    assert class_weight.numel() == Cc and out.numel() >= L
+    _check(lib().pn_ce_avg_f32(_ptr(logits), _ptr(target, torch.int64), _ptr(class_weight),
+                               _ptr(out), L, rows, Cc, loss_weight, _stream()), "pn_ce_avg_f32")
+
+
+def ce_avg_grad(logits, target, class_weight, grad, loss_weight):
+    L, rows, Cc = logits.shape
+    assert logits.is_contiguous() and target.is_contiguous() and grad.is_contiguous()
+    assert target.numel() == L * rows and class_weight.numel() == Cc and grad.shape == logits.shape
+    _check(lib().pn_ce_avg_grad_f32(_ptr(logits), _ptr(target, torch.int64), _ptr(class_weight),
+                                    _ptr(grad), L, rows, Cc, loss_weight, _stream()),
+           "pn_ce_avg_grad_f32")
