@@ -732,6 +732,46 @@ int pn_eval_iou_best(const int32_t* inter, const int32_t* area_pred, const int32
                      const int32_t* gt_sub_row, const int32_t* gt_obj_row, int G, uint8_t* valid,
                      double* best, void* stream);
 
+/* Panoptic quality (csrc/panoptic_quality.hip): one image's share of PQ / SQ / RQ, the metric of
+ * the reference's `--eval PQ` (pairnet/datasets/psg.py:309-335 -> [3P] mmdet's panoptic
+ * evaluation), from the panoptic map `pairnet_head.py:882` writes (value = segment *
+ * INSTANCE_OFFSET + class; csrc/postproc.hip).  The metric is restated from memory, unpinned;
+ * INTEGRATION.md 3a-2 states it in full and is the specification.  Entries added at ABI 34.
+ * The confusion table, one pass, every pixel read once:
+ *   pred [H][W] int64 (16-byte aligned): s = value / instance_offset < 256, c = value %
+ *        instance_offset; c == num_classes is void
+ *   gt_rgb [H][W][3] uint8 (4-byte aligned): the panoptic PNG, id = R + 256 G + 65536 B
+ *   gt_ids [G] int32, strictly ascending, in [1, 2^24); G <= 255 (G == 0: any readable word)
+ *   N [G + 1][257] int32: N[g][p] = pixels of ground-truth row g (0 = void: id 0 or not in
+ *        gt_ids; g = 1 + index into gt_ids) under predicted column p (p = s; 256 = void)
+ *   col_cat [256] int32: the category of column s, -1 for a segment without pixels
+ *   status [1] int32: 0, | 1 a value < 0 or with c > num_classes, | 2 s >= 256, | 4 two
+ *        categories under one s; flagged pixels are counted nowhere.
+ * All three outputs are written whole (no zeroing by the caller).  Integer atomics only: the
+ * result does not depend on any order of execution.  The table is kept in LDS per workgroup
+ * for G <= 61 and summed into N at the end; above, the adds go to N directly.
+ * flags: PN_PQ_PLAIN = one atomic add per pixel (the form the aggregated one is measured
+ * against), else 0.  H * W < 2^31, 1 <= num_classes <= 999 < instance_offset. */
+#define PN_PQ_PLAIN 1
+int pn_pq_confusion(const int64_t* pred, const uint8_t* gt_rgb, int H, int W,
+                    const int32_t* gt_ids, int G, int num_classes, int instance_offset,
+                    int flags, int32_t* N, int32_t* col_cat, int32_t* status, void* stream);
+/* The image's record from N and col_cat above, gt_cat / gt_crowd [G] int32 (category in
+ * [0, num_classes), iscrowd) in gt_ids' order; one workgroup:
+ *   area_gt [G + 1], area_pred [257] int32: row and column sums of N
+ *   match [G + 1] int32: the column matched to row g, or -1 (row 0: -1).  (g, p) match when g is
+ *        not void and not crowd, the categories are equal, N[g][p] > 0 and 2 N[g][p] > union,
+ *        union = area_pred[p] + area_gt[g] - N[g][p] - N[0][p] (iou > 0.5, decided in integers)
+ *   rec [num_classes][3] int32 = (tp, fp, fn): fn = unmatched non-crowd rows; fp = unmatched
+ *        columns unless 2 (N[0][p] + sum over crowd rows of its category N[g'][p]) > area_pred[p]
+ *   iou [num_classes] float64: the sum of (double)N / (double)union over the matches, added in
+ *        ascending ground-truth id
+ *   status [1]: |= 8 for a gt_cat outside [0, num_classes) (not re-zeroed here). */
+int pn_pq_record(const int32_t* N, const int32_t* col_cat, const int32_t* gt_cat,
+                 const int32_t* gt_crowd, int G, int num_classes, int32_t* area_gt,
+                 int32_t* area_pred, int32_t* match, int32_t* rec, double* iou, int32_t* status,
+                 void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Box trunk of the sibling head CrossHeadBBox (pairnet_bbox_head.py:193-359): the
  * input-dependent glue of mmdet's two-stage, box-refining DeformableDetrTransformer

@@ -20,7 +20,8 @@ from .train_pipeline import AugParams, HalfSizeMasks, TrainPipeline  # noqa: F40
 from .detector import (PSGTr, Result, ResultStreamer, build_detector, load_checkpoint,  # noqa: F401
                        triplet2Result)
 from .dist import all_gather_triplets, shard_indices  # noqa: F401
-from .evaluation import SceneGraphMetrics, StreamingEvaluator, TripletEvaluator  # noqa: F401
+from .evaluation import (PanopticQuality, SceneGraphMetrics, StreamingEvaluator,  # noqa: F401
+                         TripletEvaluator)
 from . import dataset  # noqa: F401  (PSG ground truth: load_psg, ann_info, eval_ground_truth, ...)
 
 __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "CrossHead2",
@@ -29,5 +30,5 @@ __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "Cros
            "baseline_r50", "PSGTrHead2", "psgtr2_head_cfg", "psgtr2_r50", "ResNet50Hip",
            "SwinTransformerHip", "pairnet_swin", "swin_backbone_cfg", "TestPipeline", "test_pipeline_cfg",
            "CrossHeadBBox", "ChannelMapper", "bbox_head_cfg", "channel_mapper_cfg", "cross_r101_vg",
-           "TripletEvaluator", "SceneGraphMetrics", "StreamingEvaluator", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "TailTrainer", "FfnDropout",
+           "TripletEvaluator", "SceneGraphMetrics", "StreamingEvaluator", "PanopticQuality", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "TailTrainer", "FfnDropout",
            "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg", "Mask2FormerLoss"]

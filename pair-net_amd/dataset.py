@@ -133,3 +133,15 @@ def load_masks_and_semantic_seg(ann, pan_rgb, device):
     with torch.cuda.device(device):
         hip.pan_masks(rgb, ids, cats, masks, sem)
     return masks, sem
+
+
+def panoptic_ground_truth(d, pan_rgb, device):
+    """One image's ground truth for `evaluation.PanopticQuality` (`--eval PQ`, psg.py:309-335):
+    `d` is a raw entry of `load_psg(...)["data"]` (`ann_info` drops `iscrowd`, so its output
+    cannot be used), `pan_rgb` the decoded panoptic PNG (H, W, 3) uint8.  Returns
+    dict(gt_pan=<the RGB map on the device>, gt_segments=<(G, 3) int64 (id, category, iscrowd)
+    sorted by id>): the keys `dist.multi_gpu_test(panoptic=...)` reads."""
+    seg = np.array([(s["id"], s["category_id"], s.get("iscrowd", 0)) for s in d["segments_info"]],
+                   dtype=np.int64).reshape(-1, 3)
+    seg = seg[np.argsort(seg[:, 0], kind="stable")]
+    return dict(gt_pan=_rgb(pan_rgb, torch.device(device)), gt_segments=seg)

@@ -369,7 +369,7 @@ def collate(items):
 
 def multi_gpu_test(detector, dataset, annotations=None, evaluator=None, metrics=None, *,
                    depth=4, group=None, host_staging=None, force_collective=False,
-                   rescale=False, calibrate=True, samples_per_gpu=1):
+                   rescale=False, calibrate=True, samples_per_gpu=1, panoptic=None):
     """The reference's distributed test loop -- mmdet `multi_gpu_test` + `collect_results_*`
     (tools/test.py:256-267) followed by `dataset.evaluate` (:277-295 ->
     pairnet/datasets/psg.py:285-404) -- for one process per GPU:
@@ -392,7 +392,13 @@ def multi_gpu_test(detector, dataset, annotations=None, evaluator=None, metrics=
         With a `StreamingEvaluator` (any evaluator that has `add` and `state`) the loop calls
         `evaluator.add(result, ..., index=i)` instead, which reads nothing back; after the last
         step every rank's `state()` blob (a few KB per image) is gathered, rank 0 merges them
-        and returns `evaluator.summary()`; `metrics` is not needed then.
+        and returns `evaluator.summary()`; `metrics` is not needed then;
+      * with `panoptic` (`evaluation.PanopticQuality`, or a stand-in with `add`, `state`, `merge`
+        and `summary`) every annotation that carries `gt_pan` (`dataset.panoptic_ground_truth`)
+        has its panoptic map, field 4 of the result, scored on the chain stream that produced
+        it: `panoptic.add(res[4], ann["gt_pan"], ann["gt_segments"], index=i)`, nothing read
+        back; the `state()` blobs are gathered at the end like the evaluator's and rank 0
+        returns `panoptic.summary()` (PQ / SQ / RQ, psg.py:309-335) as `out["panoptic"]`.
 
     `dataset[i]` -> `(img, img_metas)` as `simple_test` takes them (one image), or
     `(decoded uint8 (H, W, 3) BGR image, None)`: the detector then runs the reference's test
@@ -441,17 +447,22 @@ def multi_gpu_test(detector, dataset, annotations=None, evaluator=None, metrics=
         # produced on the CALLER's stream, the evaluator reads it on the chain stream that
         # produced the result: order the two
         ann_ready = None
-        if evaluator is not None and col.on_gpu and any(a is not None for a in anns):
+        if (evaluator is not None or panoptic is not None) and col.on_gpu and \
+                any(a is not None for a in anns):
             ann_ready = torch.cuda.Event()
             ann_ready.record(torch.cuda.current_stream(col.device))
 
         def evaluate(tb, grp=grp, anns=anns, ann_ready=ann_ready):
-            if evaluator is None:
+            if evaluator is None and panoptic is None:
                 return
             if ann_ready is not None:
                 torch.cuda.current_stream(col.device).wait_event(ann_ready)
             for res, idx, ann in zip(tb.results, grp, anns):
                 if ann is None:
+                    continue
+                if panoptic is not None and ann.get("gt_pan") is not None:
+                    panoptic.add(res[4], ann["gt_pan"], ann["gt_segments"], index=idx)
+                if evaluator is None:
                     continue
                 if streaming:
                     evaluator.add(res, ann["gt_rels"], ann["gt_labels"], ann["gt_masks"],
@@ -490,6 +501,15 @@ def multi_gpu_test(detector, dataset, annotations=None, evaluator=None, metrics=
                                                 key=lambda e: e[0]):
                 metrics.add(ev, gt_rels, iou=iou)
             out["metrics"] = metrics.summary()
+    if panoptic is not None:
+        blob = panoptic.state()                # (its one wait for the GPU)
+        states = [blob]
+        if W > 1:
+            states = [None] * W
+            dist.all_gather_object(states, blob, group=group)
+        if rank == 0:
+            panoptic.merge(states)
+            out["panoptic"] = panoptic.summary()
     return out
 
 

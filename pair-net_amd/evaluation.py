@@ -16,6 +16,10 @@ have the predicate, then over the predicates), phrase-detection variants, and th
 subject / object IoU statistic (`_compute_iou_panseg`, :1087-1131, from the same exact
 popcounts).  Images without ground-truth relations are skipped, as the reference's
 `sgg_evaluate` loop does.
+
+`PanopticQuality` is the reference's other metric, `--eval PQ` (pairnet/datasets/psg.py:309-335):
+PQ / SQ / RQ of the panoptic maps, from a per-image record csrc/panoptic_quality.hip leaves on
+the device.
 """
 import numpy as np
 import torch
@@ -582,3 +586,308 @@ class StreamingEvaluator:
             m.obj_iou.extend(obj)
         m.skipped = len(self._skipped)
         return m.summary()
+
+
+# ---- panoptic quality ----------------------------------------------------------------------
+PQ_BAD_VALUE, PQ_BAD_SEGMENT, PQ_TWO_CATEGORIES, PQ_BAD_GT_CATEGORY = 1, 2, 4, 8
+_PQ_STATUS = ((PQ_BAD_VALUE, "a value below 0 or with a class above num_classes"),
+              (PQ_BAD_SEGMENT, "a segment index of 256 or more"),
+              (PQ_TWO_CATEGORIES, "two classes under one segment index"),
+              (PQ_BAD_GT_CATEGORY, "a ground-truth category outside [0, num_classes)"))
+
+
+def rgb2id(rgb):
+    """The panoptic PNG's ids: R + 256 G + 65536 B of an (H, W, 3) uint8 array, int64."""
+    rgb = np.asarray(rgb).astype(np.int64)
+    return rgb[..., 0] + 256 * rgb[..., 1] + 65536 * rgb[..., 2]
+
+
+def host_confusion(pred, gt_ids, seg, num_classes, instance_offset):
+    """`pn_pq_confusion` in numpy: (N [(G + 1)][257] int32, col_cat [256] int32, status).
+    seg: (G, 3) (id, category, iscrowd) sorted by id.  Row 0 / column 256 are void."""
+    v = np.asarray(pred).astype(np.int64).reshape(-1)
+    gid = np.asarray(gt_ids).astype(np.int64).reshape(-1)
+    G = seg.shape[0]
+    neg = v < 0
+    s, c = np.where(neg, 0, v) // instance_offset, np.where(neg, 0, v) % instance_offset
+    bad_c, bad_s = neg | (c > num_classes), ~neg & (s >= 256)
+    status = (PQ_BAD_VALUE if bad_c.any() else 0) | (PQ_BAD_SEGMENT if bad_s.any() else 0)
+    ok = ~(bad_c | bad_s)
+    seg_px = ok & (c < num_classes)
+    col_cat = np.full(256, -1, np.int32)
+    np.maximum.at(col_cat, s[seg_px], c[seg_px].astype(np.int32))
+    if (col_cat[s[seg_px]] != c[seg_px]).any():
+        status |= PQ_TWO_CATEGORIES
+    col = np.where(seg_px, s, 256)
+    pos = np.searchsorted(seg[:, 0], gid)
+    hit = (gid != 0) & (pos < G)
+    hit[hit] = seg[pos[hit], 0] == gid[hit]
+    row = np.where(hit, pos + 1, 0)
+    N = np.bincount((row * 257 + col)[ok], minlength=(G + 1) * 257)
+    return N.reshape(G + 1, 257).astype(np.int32), col_cat, status
+
+
+def host_pq_record(N, col_cat, seg, num_classes):
+    """`pn_pq_record` in numpy: (rec [num_classes][3] int32 = tp, fp, fn; iou [num_classes]
+    float64; match [G + 1])."""
+    N = N.astype(np.int64)
+    G = seg.shape[0]
+    area_g, area_p = N.sum(1), N.sum(0)
+    cat, crowd = seg[:, 1], seg[:, 2] != 0
+    union = area_p[None, :256] + area_g[1:, None] - N[1:, :256] - N[0:1, :256]
+    same = (cat[:, None] == col_cat[None, :].astype(np.int64)) & ~crowd[:, None]
+    hit = same & (N[1:, :256] > 0) & (2 * N[1:, :256] > union)
+    if G and (hit.sum(0).max() > 1 or hit.sum(1).max() > 1):
+        raise AssertionError("two matches for one segment: iou > 0.5 cannot hold twice")
+    rec = np.zeros((num_classes, 3), np.int32)
+    iou = np.zeros(num_classes, np.float64)
+    match = np.full(G + 1, -1, np.int32)
+    for g in range(G):                         # ascending ground-truth id
+        if crowd[g]:
+            continue
+        p = np.nonzero(hit[g])[0]
+        if p.shape[0]:
+            match[g + 1] = p[0]
+            rec[cat[g], 0] += 1
+            iou[cat[g]] += np.float64(N[g + 1, p[0]]) / np.float64(union[g, p[0]])
+        else:
+            rec[cat[g], 2] += 1
+    unmatched = (col_cat >= 0) & (area_p[:256] > 0) & ~hit.any(0)
+    for p in np.nonzero(unmatched)[0]:
+        absorbed = N[0, p] + N[1:, p][crowd & (cat == col_cat[p])].sum()
+        if not 2 * absorbed > area_p[p]:
+            rec[col_cat[p], 1] += 1
+    return rec, iou, match
+
+
+class PanopticQuality:
+    """PQ / SQ / RQ of the panoptic maps `get_bboxes` returns as field 4 (`Result.pan_results`):
+    the metric of the reference's `--eval PQ` (pairnet/datasets/psg.py:309-335 -> mmdet's panoptic
+    evaluation), restated from memory (INTEGRATION.md 3a-2 is the specification), for a loop that
+    must not wait for the GPU.  `add()` enqueues one pass over the pixels (`pn_pq_confusion`: the
+    ground-truth x predicted segment overlap table) and the matching (`pn_pq_record`) on the
+    current stream and leaves the image's record -- (tp, fp, fn) per category as int32, the IoU
+    sums as float64 -- and a status word on the device; nothing is read back before `state()` /
+    `summary()`.
+
+        pq = PanopticQuality()                       # PSG: 133 classes, 80 of them things
+        for each image i:  pq.add(result[4], gt_pan_rgb, gt_segments, index=i)
+        pq.summary()   ->  {"PQ": .., "SQ": .., "RQ": .., "PQ_th": .., ..., "PQ_st": .., ...,
+                            "n": {"all": .., "things": .., "stuff": ..}, "images": n,
+                            "classwise": {category: (pq, sq, rq)}}     (percentages)
+
+    Several ranks: `pq.merge(all ranks' pq.state())` on rank 0, then `pq.summary()`; records are
+    summed in ascending image index, so the result equals a single-rank run bit for bit.
+    `keep_confusion`: keep every image's table N for `records()` (tests; ~1 KB per ground-truth
+    segment and image of device memory until the flush)."""
+
+    _MAGIC = 0x5051
+
+    def __init__(self, num_classes=133, num_things=80, instance_offset=1000,
+                 keep_confusion=False):
+        self.num_classes, self.num_things = int(num_classes), int(num_things)
+        self.instance_offset = int(instance_offset)   # head.INSTANCE_OFFSET
+        if not 1 <= self.num_classes <= 999 or not 0 <= self.num_things <= self.num_classes \
+                or self.instance_offset <= self.num_classes:
+            raise ValueError("PanopticQuality: 1 <= num_classes <= 999 < instance_offset")
+        self.keep_confusion = bool(keep_confusion)
+        self._host = {}       # index -> (status, ints [3 num_classes] int32, iou f64, N or None)
+        self._dev = []        # (index, ints + status, iou, N or None, event): not read back yet
+        self._seen = set()
+        self._calls = 0
+
+    def _segments(self, gt_segments):
+        """(G, 3) int64 (id, category, iscrowd) sorted by id, from an array or from the
+        `segments_info` dicts; checked on the host."""
+        if torch.is_tensor(gt_segments):
+            if gt_segments.is_cuda:
+                raise ValueError("gt_segments is host data (only the maps live on the device)")
+            gt_segments = gt_segments.numpy()
+        if len(gt_segments) and isinstance(gt_segments[0], dict):
+            gt_segments = [(s["id"], s["category_id"], s.get("iscrowd", 0)) for s in gt_segments]
+        seg = np.asarray(gt_segments, dtype=np.int64).reshape(-1, 3)
+        seg = seg[np.argsort(seg[:, 0], kind="stable")]
+        if seg.shape[0] > 255:
+            raise ValueError("PanopticQuality: at most 255 ground-truth segments per image")
+        if seg.shape[0] and (seg[0, 0] < 1 or seg[-1, 0] >= 1 << 24 or
+                             (np.diff(seg[:, 0]) == 0).any()):
+            raise ValueError("gt_segments: ids must be distinct and lie in [1, 2^24)")
+        if seg.shape[0] and (seg[:, 1].min() < 0 or seg[:, 1].max() >= self.num_classes):
+            raise ValueError("gt_segments: categories must lie in [0, %d)" % self.num_classes)
+        return seg
+
+    def _index(self, index):
+        idx = self._calls if index is None else int(index)
+        self._calls += 1
+        if idx in self._seen:
+            raise ValueError("PanopticQuality: image %d was added before" % idx)
+        self._seen.add(idx)
+        return idx
+
+    @torch.no_grad()
+    @hip.on_device
+    def add(self, pan_seg, gt_pan_rgb, gt_segments, index=None, flags=0):
+        """pan_seg: the device map [H, W] int64 (`result[4]`, or the 8-tuple itself);
+        gt_pan_rgb: the panoptic PNG (H, W, 3) uint8, on the device as
+        `dataset.panoptic_ground_truth` leaves it (a host array goes up pinned, non-blocking);
+        gt_segments: host data, (G, 3) (id, category, iscrowd) or the `segments_info` dicts.
+        Everything is enqueued on the current stream; nothing is read back."""
+        if isinstance(pan_seg, (tuple, list)):
+            pan_seg = pan_seg[4]
+        if not torch.is_tensor(pan_seg) or not pan_seg.is_cuda or pan_seg.dim() != 2 or \
+                pan_seg.dtype != torch.int64:
+            raise ValueError("pan_seg: a device tensor [H, W] int64")
+        dev = pan_seg.device
+        gt = gt_pan_rgb if torch.is_tensor(gt_pan_rgb) else \
+            torch.from_numpy(np.ascontiguousarray(gt_pan_rgb))
+        if gt.dtype != torch.uint8 or gt.dim() != 3 or gt.shape[2] != 3:
+            raise ValueError("gt_pan_rgb: the panoptic PNG as (H, W, 3) uint8")
+        if tuple(gt.shape[:2]) != tuple(pan_seg.shape):
+            raise ValueError("PanopticQuality: prediction %s and ground truth %s differ in size"
+                             % (tuple(pan_seg.shape), tuple(gt.shape[:2])))
+        if pan_seg.numel() == 0 or pan_seg.numel() >= 1 << 31:
+            raise ValueError("PanopticQuality: 0 < H * W < 2^31")
+        seg = self._segments(gt_segments)
+        idx = self._index(index)
+        G, nc = seg.shape[0], self.num_classes
+        if not gt.is_cuda:
+            gt = gt.contiguous().pin_memory().to(dev, non_blocking=True)
+        gt = gt.contiguous()
+        pred = pan_seg.contiguous()
+        if pred.data_ptr() % 16:
+            pred = pred.clone()
+        if gt.data_ptr() % 4:
+            gt = gt.clone()
+        n = max(G, 1)                              # [ids | categories | iscrowd], one copy
+        host = np.zeros((3, n), np.int32)
+        host[:, :G] = seg.T
+        buf = torch.empty((3, n), dtype=torch.int32, pin_memory=True)
+        buf.copy_(torch.from_numpy(host))
+        tab = buf.to(dev, non_blocking=True)
+        i32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int32)
+        N, col_cat = i32((G + 1) * hip.PQ_COLS), i32(256)
+        ints = i32(3 * nc + 1)                     # the record, then the status word
+        iou = torch.empty(nc, device=dev, dtype=torch.float64)
+        hip.pq_confusion(pred, gt, tab[0], G, nc, self.instance_offset, N, col_cat,
+                         ints[3 * nc:], flags=flags)
+        hip.pq_record(N, col_cat, tab[1], tab[2], G, nc, i32(G + 1), i32(hip.PQ_COLS),
+                      i32(G + 1), ints[:3 * nc], iou, ints[3 * nc:])
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        self._dev.append((idx, ints, iou, N if self.keep_confusion else None, ev))
+
+    def add_host(self, index, pred, gt_ids, gt_segments):
+        """The same record computed in numpy from host maps: pred [H, W] integer, gt_ids [H, W]
+        the ground-truth id map (`rgb2id` of the PNG).  The restatement the kernels are tested
+        against, and the entry of loops that run on the host."""
+        pred = pred.cpu().numpy() if torch.is_tensor(pred) else np.asarray(pred)
+        gt_ids = gt_ids.cpu().numpy() if torch.is_tensor(gt_ids) else np.asarray(gt_ids)
+        if pred.ndim != 2 or pred.shape != gt_ids.shape:
+            raise ValueError("PanopticQuality: prediction %s and ground truth %s differ in size"
+                             % (pred.shape, gt_ids.shape))
+        seg = self._segments(gt_segments)
+        idx = self._index(index)
+        N, col_cat, status = host_confusion(pred, gt_ids, seg, self.num_classes,
+                                            self.instance_offset)
+        rec, iou, _ = host_pq_record(N, col_cat, seg, self.num_classes)
+        self._host[idx] = (int(status), rec.reshape(-1), iou, N if self.keep_confusion else None)
+
+    # ---- the one place that waits for the GPU ----
+    def _flush(self):
+        if not self._dev:
+            return
+        dev = self._dev[0][1].device
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            for _, ints, iou, N, ev in self._dev:
+                # add() may have run on other streams (the pipeline's chain streams): order
+                # this stream behind each of them, and tell the allocator who reads the blocks
+                cur.wait_event(ev)
+                for t in (ints, iou, N):
+                    if t is not None:
+                        t.record_stream(cur)
+            ints = torch.stack([d[1] for d in self._dev]).cpu().numpy()
+            ious = torch.stack([d[2] for d in self._dev]).cpu().numpy()
+            tables = [None if d[3] is None else d[3].cpu().numpy().reshape(-1, hip.PQ_COLS)
+                      for d in self._dev]
+        for i, d in enumerate(self._dev):
+            self._host[d[0]] = (int(ints[i, -1]), ints[i, :-1].copy(), ious[i].copy(), tables[i])
+        self._dev = []
+
+    def records(self):
+        """{index: dict(status, rec [num_classes][3] int32 (tp, fp, fn), iou [num_classes]
+        float64, N [(G + 1)][257] or None)} of the images added so far (waits for the GPU)."""
+        self._flush()
+        return {idx: dict(status=st, rec=ints.reshape(self.num_classes, 3), iou=iou, N=N)
+                for idx, (st, ints, iou, N) in self._host.items()}
+
+    def _header(self):
+        return [self._MAGIC, self.num_classes, self.num_things, self.instance_offset]
+
+    def state(self):
+        """Everything added so far as ONE float64 array (int32 values are exact in it):
+        [magic, num_classes, num_things, instance_offset, images | per image in ascending
+        index: index, status, record, IoU sums]."""
+        self._flush()
+        parts = [np.array(self._header() + [len(self._host)], np.float64)]
+        for idx in sorted(self._host):
+            st, ints, iou, _ = self._host[idx]
+            parts += [np.array([idx, st], np.float64), ints.astype(np.float64), iou]
+        return np.concatenate(parts)
+
+    def merge(self, states):
+        """Replace this object's contents by the union of `states` (the `state()` blobs of all
+        ranks, its own among them).  An image present in two blobs is an error."""
+        self._flush()
+        host, nc = {}, self.num_classes
+        for blob in states:
+            blob = np.asarray(blob, np.float64)
+            if blob.ndim != 1 or blob.shape[0] < 5 or \
+                    [int(v) for v in blob[:4]] != self._header() or \
+                    blob.shape[0] != 5 + int(blob[4]) * (2 + 4 * nc):
+                raise ValueError("PanopticQuality.merge: not a state of this configuration")
+            o = 5
+            for _ in range(int(blob[4])):
+                idx, st = int(blob[o]), int(blob[o + 1])
+                if idx in host:
+                    raise ValueError("PanopticQuality.merge: image %d occurs twice" % idx)
+                host[idx] = (st, blob[o + 2:o + 2 + 3 * nc].astype(np.int32),
+                             blob[o + 2 + 3 * nc:o + 2 + 4 * nc].copy(), None)
+                o += 2 + 4 * nc
+        self._host = host
+        self._seen = set(host)
+
+    def summary(self):
+        """Per category tp / fp / fn summed as integers and the IoU sums added as float64 in
+        ascending image index; pq = iou / (tp + fp / 2 + fn / 2), sq = iou / tp, rq = tp /
+        (tp + fp / 2 + fn / 2); averaged over the categories with tp + fp + fn > 0 (in ascending
+        category), times 100.  An image whose status word is set raises here."""
+        self._flush()
+        nc = self.num_classes
+        for idx in sorted(self._host):
+            st = self._host[idx][0]
+            if st:
+                raise ValueError("PanopticQuality: the panoptic map of image %d has %s (status %d)"
+                                 % (idx, "; ".join(w for b, w in _PQ_STATUS if st & b), st))
+        cnt = np.zeros((nc, 3), np.int64)
+        iou = np.zeros(nc, np.float64)
+        for idx in sorted(self._host):
+            _, ints, io, _ = self._host[idx]
+            cnt += ints.reshape(nc, 3)
+            iou += io
+        classwise = {}
+        for c in range(nc):
+            tp, fp, fn = (int(v) for v in cnt[c])
+            if tp + fp + fn == 0:
+                continue
+            den = tp + 0.5 * fp + 0.5 * fn
+            classwise[c] = (float(iou[c]) / den, float(iou[c]) / tp if tp else 0.0, tp / den)
+        out = dict(images=len(self._host), classwise=classwise, n={})
+        for name, suffix, keep in (("all", "", lambda c: True),
+                                   ("things", "_th", lambda c: c < self.num_things),
+                                   ("stuff", "_st", lambda c: c >= self.num_things)):
+            rows = [classwise[c] for c in sorted(classwise) if keep(c)]
+            out["n"][name] = len(rows)
+            for j, key in enumerate(("PQ", "SQ", "RQ")):
+                out[key + suffix] = 100.0 * (sum(r[j] for r in rows) / len(rows)) if rows else 0.0
+        return out

@@ -231,6 +231,9 @@ _SIGS = {
     "pn_point_scatter_grad_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "pn_ce_avg_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "pn_ce_avg_grad_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
+    "pn_pq_confusion": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                  _vp]),
+    "pn_pq_record": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 34  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
@@ -1192,6 +1195,43 @@ def eval_iou_best(inter, area_p, area_g, P, n_obj, pred_labels, gt_labels, gs, g
                                   _ptr(pred_labels, torch.int64), _ptr(gt_labels, i32),
                                   _ptr(gs, i32), _ptr(go, i32), G, _ptr(valid, torch.uint8),
                                   _ptr(best, torch.float64), _stream()), "pn_eval_iou_best")
+
+
+# ---- panoptic quality (csrc/panoptic_quality.hip) ----
+PQ_COLS = 257          # column s = predicted segment s, column 256 = void
+PQ_LDS_MAX_G = 61      # largest G whose (G + 1) x 257 table is kept in LDS (64 KB a workgroup)
+PQ_PLAIN = 1           # PN_PQ_PLAIN
+
+
+def pq_confusion(pred, gt_rgb, gt_ids, G, num_classes, instance_offset, N, col_cat, status,
+                 flags=0):
+    """N [(G + 1)][257], col_cat [256], status [1] int32 (all written whole) from the predicted
+    map [H][W] int64 and the ground-truth PNG [H][W][3] uint8; gt_ids [>= G] int32 ascending."""
+    i32 = torch.int32
+    H, W = int(pred.shape[0]), int(pred.shape[1])
+    assert pred.is_contiguous() and gt_rgb.is_contiguous() and tuple(gt_rgb.shape) == (H, W, 3)
+    assert N.numel() == (G + 1) * PQ_COLS and col_cat.numel() == 256 and status.numel() == 1
+    assert gt_ids.numel() >= max(G, 1)
+    _check(lib().pn_pq_confusion(_ptr(pred, torch.int64), _ptr(gt_rgb, torch.uint8), H, W,
+                                 _ptr(gt_ids, i32), G, num_classes, instance_offset, flags,
+                                 _ptr(N, i32), _ptr(col_cat, i32), _ptr(status, i32), _stream()),
+           "pn_pq_confusion")
+
+
+def pq_record(N, col_cat, gt_cat, gt_crowd, G, num_classes, area_gt, area_pred, match, rec, iou,
+              status):
+    """(tp, fp, fn) [num_classes][3] int32 and the IoU sums [num_classes] float64 of one image
+    from its confusion table; areas [G + 1] / [257] and the matched column per row [G + 1]."""
+    i32 = torch.int32
+    assert N.numel() == (G + 1) * PQ_COLS and col_cat.numel() == 256 and status.numel() == 1
+    assert gt_cat.numel() >= max(G, 1) and gt_crowd.numel() >= max(G, 1)
+    assert area_gt.numel() == G + 1 and match.numel() == G + 1 and area_pred.numel() == PQ_COLS
+    assert rec.numel() == 3 * num_classes and iou.numel() == num_classes
+    _check(lib().pn_pq_record(_ptr(N, i32), _ptr(col_cat, i32), _ptr(gt_cat, i32),
+                              _ptr(gt_crowd, i32), G, num_classes, _ptr(area_gt, i32),
+                              _ptr(area_pred, i32), _ptr(match, i32), _ptr(rec, i32),
+                              _ptr(iou, torch.float64), _ptr(status, i32), _stream()),
+           "pn_pq_record")
 
 
 # ---- box trunk glue (csrc/detr.hip) ----
