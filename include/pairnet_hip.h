@@ -1236,6 +1236,56 @@ int pn_ce_avg_f32(const float* logits, const int64_t* target, const float* class
 int pn_ce_avg_grad_f32(const float* logits, const int64_t* target, const float* class_weight,
                        float* grad, int L, int rows, int C, float loss_weight, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * The relation terms of the sibling head's loss (csrc/rel_loss.hip; pair-net_amd/baseline_losses.py
+ * drives them): r_loss_cls, loss_subject_match and loss_object_match of the reference's
+ * relation_heads/baseline.py:655-694, 828-907 under configs/mask2former/baseline_r50_psg.py:336-350,
+ * 373-378, last decoder layer only (baseline.py:523-526), values and d loss / d logits.  The
+ * assignment is ONE pn_lsa_f32 launch over the B images; r_loss_cls is pn_ce_avg_f32 /
+ * pn_ce_avg_grad_f32 with L = 1 on the labels written here.  Fixed-order reductions, no
+ * floating-point atomics.  Entries added at ABI 34 (adding entries is compatible).
+ *
+ * tab [B][8] int64 on the device, one row per image: {offset of its R x Gr block in `cost`, Gr,
+ * offset of its rows in gt_rels [rel_len][3] = (subject object, object object, predicate), offset
+ * of its last-layer rows in pn_seg_targets' `matched` [Mtot][4], their number n = min(Q, G), offset
+ * of its objects in the concatenated ground truth (what matched[.][3] counts from), G, offset of
+ * its P = min(R, Gr) entries in row_ind / col_ind / pos / row_loss}.  Q, R, G <= 1024.
+ * ------------------------------------------------------------------------- */
+/* OldIdMatcher's cost (approaches/matcher.py:323-330, ClassificationCost three times) for every
+ * image in one launch, laid out as pn_lsa_f32's table wants:
+ *   cost[r][k] = (-w_s softmax(sub[b][r])[a[s_k]] - w_o softmax(obj[b][r])[a[o_k]])
+ *                - w_r softmax(rel[b][r])[p_k]
+ * a = ones_like(gt_labels); a[pos_assigned_gt_inds] = od_pos_inds (baseline.py:829-830), read from
+ * the image's `matched` rows.  rel [B][R][C1], sub / obj [B][R][Q].  An image whose matched rows
+ * are -1 (its segmentation assignment failed) gets zeros. */
+int pn_rel_id_cost_f32(const float* rel, const float* sub, const float* obj, const int64_t* gt_rels,
+                       int64_t rel_len, const int64_t* matched, int64_t Mtot, const int64_t* tab,
+                       float* cost, int64_t cost_len, int B, int R, int Q, int C1, float w_s,
+                       float w_o, float w_r, void* stream);
+/* The targets behind the id assignment (baseline.py:866-907): r_labels [B * R] int64 = the matched
+ * relation's predicate, 0 for the rest; pos [out_len][4] int32 = (image, relation row, position of
+ * the subject's query among the image's matched queries, the object's) per positive row in
+ * ascending row order (:883-897), -1 for an image that was skipped.  status [1] int32: the OR of
+ * pn_lsa_f32's status of every image, | 4 an index or predicate out of range, | 8 a table row out
+ * of range, | 16 a related object's query is not among the matched queries (the reference raises
+ * at :886), | 32 the image's last-layer segmentation assignment failed.  An image with a non-zero
+ * status keeps its fills. */
+int pn_rel_targets(const int64_t* tab, const int32_t* row_ind, const int32_t* col_ind,
+                   int64_t out_len, const int32_t* lsa_status, const int64_t* gt_rels,
+                   int64_t rel_len, const int64_t* matched, int64_t Mtot, int B, int R, int Q, int C1,
+                   int64_t* r_labels, int32_t* pos, int32_t* status, void* stream);
+/* loss_subject_match / loss_object_match (baseline.py:655-682): MultilabelCrossEntropy
+ * (losses/seg_losses.py:47-57) with a one-hot target on scores[pos_inds][:, od_pos_inds], mean over
+ * the image's P rows times the loss weight, then the mean over the B images:
+ *   row_loss [pos_len][2] = lse over the n matched columns - the target column's score
+ *   out [2] = (1 / B) sum_b w * (sum_i row_loss / P_b), rows then images in ascending order
+ *   g_sub / g_obj [B][R][Q] (both or neither NULL) = w / (B P_b) (softmax - onehot) in the matched
+ *   columns of the positive rows, 0 everywhere else: every element is written. */
+int pn_id_ce_f32(const float* sub, const float* obj, const int64_t* matched, int64_t Mtot,
+                 const int64_t* tab, const int32_t* pos, int64_t pos_len, int B, int R, int Q,
+                 float w_s, float w_o, float* row_loss, float* out, float* g_sub, float* g_obj,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

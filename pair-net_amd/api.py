@@ -15,6 +15,7 @@ from .grad import (BackboneGrad, FfnDropout, HeadGrad, PixelDecoderGrad,  # noqa
                    RelationTailGrad, SwinBackboneGrad)
 from .train import TailTrainer  # noqa: F401
 from .seg_losses import Mask2FormerLoss  # noqa: F401
+from .baseline_losses import BaselineRelationLoss  # noqa: F401
 from .preprocess import TestPipeline  # noqa: F401
 from .train_pipeline import AugParams, HalfSizeMasks, TrainPipeline  # noqa: F401
 from .detector import (PSGTr, Result, ResultStreamer, build_detector, load_checkpoint,  # noqa: F401
@@ -31,4 +32,5 @@ __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "Cros
            "SwinTransformerHip", "pairnet_swin", "swin_backbone_cfg", "TestPipeline", "test_pipeline_cfg",
            "CrossHeadBBox", "ChannelMapper", "bbox_head_cfg", "channel_mapper_cfg", "cross_r101_vg",
            "TripletEvaluator", "SceneGraphMetrics", "StreamingEvaluator", "PanopticQuality", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "TailTrainer", "FfnDropout",
-           "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg", "Mask2FormerLoss"]
+           "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg", "Mask2FormerLoss",
+           "BaselineRelationLoss"]

@@ -40,6 +40,10 @@ class CrossHeadBaseline(CrossHead2):
         self._seg_loss_cfg = dict(train_cfg=kwargs.get("train_cfg"), loss_cls=kwargs.get("loss_cls"),
                                   loss_mask=kwargs.get("loss_mask"), loss_dice=kwargs.get("loss_dice"))
         self._seg_loss = None
+        # the relation terms' options (:336-350, 373-378; `full_losses`)
+        self._rel_loss_cfg = dict(train_cfg=kwargs.get("train_cfg"), rel_loss_cls=rel_loss_cls,
+                                  sub_id_loss=sub_id_loss, obj_id_loss=obj_id_loss)
+        self._rel_loss = None
         super().__init__(num_classes, in_channels, num_relations, num_obj_query=num_obj_query,
                          num_rel_query=num_rel_query, use_mask=use_mask, **kwargs)
 
@@ -151,7 +155,8 @@ class CrossHeadBaseline(CrossHead2):
         panoptic_heads/mask2former_head.py:223-324 per decoder layer): {loss_cls, loss_mask,
         loss_dice, d0.loss_cls, ...} from the two dicts a `return_all_layers=True` forward returns
         (seg_losses.py; `grads={}` adds d sum / d logits, `points=` / `seed=` / `step=` fix the
-        draws).  The relation terms of the full `loss` (:655-694, 828-907) are not built."""
+        draws).  The relation terms of the full `loss` (:655-694, 828-907) are added by
+        `full_losses`."""
         if self._seg_loss is None:
             from .seg_losses import Mask2FormerLoss
             cfg = dict(self._seg_loss_cfg)
@@ -162,6 +167,55 @@ class CrossHeadBaseline(CrossHead2):
                                              **cfg)
         return self._seg_loss.loss(all_cls_scores["cls"], all_mask_preds["mask"], gt_labels_list,
                                    gt_masks_list, img_metas, **kw)
+
+    # ------------------------------------------------------- the whole loss dict
+    def full_losses(self, all_cls_scores, all_mask_preds, gt_rels_list, gt_bboxes_list,
+                    gt_labels_list, gt_masks_list, img_metas, gt_bboxes_ignore=None, grads=None,
+                    **kw):
+        """The reference's `loss` dict (baseline.py:446-528, its argument order): the 3 L terms of
+        `seg_losses` plus r_loss_cls, loss_subject_match and loss_object_match of the last layer
+        (baseline_losses.py), matched on that call's segmentation assignment.  Values; `grads={}`
+        receives "cls", "mask_rows", "mask" (as `seg_losses`) and "rel", "subject_scores",
+        "object_scores" (d sum / d logits).  `points=`, `seed=`, `step=`, `num_total_masks=` go to
+        `seg_losses`.  An image without a ground-truth relation raises ValueError, as
+        `CrossHead2.loss` does.  `seg_status()` / `rel_status()` hold the two device status words."""
+        if gt_bboxes_ignore is not None:
+            raise AssertionError("Only supports for gt_bboxes_ignore setting to None.")
+        if self._rel_loss is None:
+            from .baseline_losses import BaselineRelationLoss
+            cfg = dict(self._rel_loss_cfg)
+            tc = cfg.pop("train_cfg")
+            if tc is not None:
+                if dict(tc).get("id_assigner") is None:
+                    raise NotImplementedError("train_cfg without an id_assigner")
+                tc = dict(id_assigner=dict(tc)["id_assigner"])
+            self._rel_loss = BaselineRelationLoss(self.num_relations, self.num_obj_query,
+                                                  self.num_rel_query, train_cfg=tc, **cfg)
+        rel = all_cls_scores["rel"]
+        B = int(rel.shape[0])
+        # refuse what the relation part refuses BEFORE anything is launched
+        if len(gt_rels_list) != B:
+            raise ValueError("ground-truth relations for %d images, logits for %d"
+                             % (len(gt_rels_list), B))
+        G = [int(torch.as_tensor(g).reshape(-1).shape[0]) for g in gt_labels_list]
+        for b, gr in enumerate(gt_rels_list):
+            if torch.as_tensor(gr).numel() == 0:
+                raise ValueError("image %d has no ground-truth relation" % b)
+            if G[b] > self.num_obj_query:
+                raise ValueError("image %d: %d ground-truth objects for %d queries"
+                                 % (b, G[b], self.num_obj_query))
+        out = self.seg_losses(all_cls_scores, all_mask_preds, gt_labels_list, gt_masks_list,
+                              img_metas, grads=grads, **kw)
+        out.update(self._rel_loss.loss(rel, all_cls_scores["subject_scores"],
+                                       all_cls_scores["object_scores"], gt_rels_list,
+                                       self._seg_loss.last["matched"], B, grads=grads, num_gts=G))
+        return out
+
+    def seg_status(self):
+        return None if self._seg_loss is None else self._seg_loss.assign_status
+
+    def rel_status(self):
+        return None if self._rel_loss is None else self._rel_loss.assign_status
 
     # ------------------------------------------------------- post-processing
     @torch.no_grad()

@@ -532,6 +532,28 @@ class PSGTr:
             head.return_all_layers = old
         return head.seg_losses(*outs, gt_labels, gt_masks, img_metas, **kw)
 
+    @torch.no_grad()
+    def val_full_losses(self, img, img_metas, gt_rels, gt_labels, gt_masks, **kw):
+        """The whole loss dict of a head that has it (`CrossHeadBaseline.full_losses`: the 3 L
+        segmentation terms plus r_loss_cls, loss_subject_match and loss_object_match,
+        relation_heads/baseline.py:446-528) as validation values, shaped like `val_seg_losses`:
+        extract_feat -> prepared ground-truth masks -> head forward with all decoder layers ->
+        `full_losses`.  Keywords as `val_seg_losses`; `grads={}` also receives the relation logits'
+        gradients."""
+        head = self.bbox_head
+        if not hasattr(head, "full_losses"):
+            raise NotImplementedError("%s has no full loss dict here (CrossHeadBaseline does)"
+                                      % type(head).__name__)
+        x = self.extract_feat(img)
+        gt_masks = self._prepare_gt_masks(img, gt_masks)
+        old = head.return_all_layers
+        head.return_all_layers = True
+        try:
+            outs = head.forward(x, img_metas)
+        finally:
+            head.return_all_layers = old
+        return head.full_losses(*outs, gt_rels, None, gt_labels, gt_masks, img_metas, **kw)
+
     def _prepare_gt_masks(self, img, gt_masks):
         """PSGTr.forward_train's ground-truth mask preparation (psgtr.py:126-141): zero-pad to the
         batch tensor's (H, W), nearest-resize to (H // 2, W // 2); one kernel per image."""

@@ -234,6 +234,12 @@ _SIGS = {
     "pn_pq_confusion": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                   _vp]),
     "pn_pq_record": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn_rel_id_cost_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32,
+                                     _i32, _i32, _f32, _f32, _f32, _vp]),
+    "pn_rel_targets": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32,
+                                 _vp, _vp, _vp, _vp]),
+    "pn_id_ce_f32": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _f32, _vp,
+                               _vp, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 34  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
@@ -1760,3 +1766,54 @@ def ce_avg_grad(logits, target, class_weight, grad, loss_weight):
     _check(lib().pn_ce_avg_grad_f32(_ptr(logits), _ptr(target, torch.int64), _ptr(class_weight),
                                     _ptr(grad), L, rows, Cc, loss_weight, _stream()),
            "pn_ce_avg_grad_f32")
+
+
+# ---- the sibling head's relation losses (csrc/rel_loss.hip; composed in baseline_losses.py) -------
+REL_MAX_SIDE = 1024       # Q, R and the objects of one image (csrc/rel_loss.hip)
+REL_STATUS_RANGE, REL_STATUS_TABLE, REL_STATUS_UNMATCHED, REL_STATUS_SEG = 4, 8, 16, 32
+
+
+def rel_id_cost(rel, sub, obj, gt_rels, matched, tab, cost, w_s, w_o, w_r):
+    """include/pairnet_hip.h: every image's [R, Gr_b] id match cost block of the flat `cost`, one
+    launch.  rel [B, R, C1], sub / obj [B, R, Q] fp32; gt_rels [., 3], matched [Mtot, 4], tab [B, 8]
+    int64."""
+    B, R, C1 = rel.shape
+    Q = sub.shape[2]
+    assert sub.shape == (B, R, Q) and obj.shape == (B, R, Q) and tab.shape == (B, 8)
+    assert all(t.is_contiguous() for t in (rel, sub, obj, gt_rels, matched, tab, cost))
+    assert gt_rels.dim() == 2 and gt_rels.shape[1] == 3 and matched.dim() == 2 and matched.shape[1] == 4
+    _check(lib().pn_rel_id_cost_f32(_ptr(rel), _ptr(sub), _ptr(obj), _ptr(gt_rels, torch.int64),
+                                    gt_rels.shape[0], _ptr(matched, torch.int64), matched.shape[0],
+                                    _ptr(tab, torch.int64), _ptr(cost), cost.numel(), B, R, Q, C1,
+                                    w_s, w_o, w_r, _stream()), "pn_rel_id_cost_f32")
+
+
+def rel_targets(tab, row_ind, col_ind, lsa_status, gt_rels, matched, R, Q, C1, r_labels, pos, status):
+    """include/pairnet_hip.h: r_labels [B * R] int64, pos [P, 4] int32 and status [1] int32 from the B
+    id assignments."""
+    B = tab.shape[0]
+    assert tab.shape == (B, 8) and tab.is_contiguous() and r_labels.numel() == B * R
+    assert row_ind.numel() == col_ind.numel() == pos.shape[0] and pos.shape[1] == 4
+    assert r_labels.is_contiguous() and pos.is_contiguous() and lsa_status.numel() >= B
+    assert gt_rels.is_contiguous() and matched.is_contiguous()
+    _check(lib().pn_rel_targets(_ptr(tab, torch.int64), _ptr(row_ind, torch.int32),
+                                _ptr(col_ind, torch.int32), row_ind.numel(),
+                                _ptr(lsa_status, torch.int32), _ptr(gt_rels, torch.int64),
+                                gt_rels.shape[0], _ptr(matched, torch.int64), matched.shape[0], B, R,
+                                Q, C1, _ptr(r_labels, torch.int64), _ptr(pos, torch.int32),
+                                _ptr(status, torch.int32), _stream()), "pn_rel_targets")
+
+
+def id_ce(sub, obj, matched, tab, pos, w_s, w_o, row_loss, out, g_sub=None, g_obj=None):
+    """include/pairnet_hip.h: out [2] = loss_subject_match, loss_object_match; row_loss [P, 2];
+    g_sub / g_obj [B, R, Q] (both or neither) are written in full."""
+    B, R, Q = sub.shape
+    assert obj.shape == sub.shape and sub.is_contiguous() and obj.is_contiguous()
+    assert tab.shape == (B, 8) and tab.is_contiguous() and pos.is_contiguous() and pos.shape[1] == 4
+    assert row_loss.numel() >= 2 * pos.shape[0] and out.numel() >= 2 and matched.is_contiguous()
+    for g in (g_sub, g_obj):
+        assert g is None or (g.shape == sub.shape and g.is_contiguous())
+    _check(lib().pn_id_ce_f32(_ptr(sub), _ptr(obj), _ptr(matched, torch.int64), matched.shape[0],
+                              _ptr(tab, torch.int64), _ptr(pos, torch.int32), pos.shape[0], B, R, Q,
+                              w_s, w_o, _ptr(row_loss), _ptr(out), _ptr(g_sub), _ptr(g_obj),
+                              _stream()), "pn_id_ce_f32")
