@@ -1286,6 +1286,37 @@ int pn_id_ce_f32(const float* sub, const float* obj, const int64_t* matched, int
                  float w_s, float w_o, float* row_loss, float* out, float* g_sub, float* g_obj,
                  void* stream);
 
+/* -------------------------------------------------------------------------
+ * Backward of the mask logits (csrc/seg_grad.hip): the two products that differentiate
+ *   mask_pred = torch.einsum("bqc,bchw->bqhw", mask_embed, mask_feature)
+ * (pairnet_head.py:236-243 / baseline.py:254-296, once per decoder layer) from the COMPACT gradient
+ * the segmentation loss returns: G [M][P] fp32 (P = h * w) for the matched rows only and mask_rows
+ * [M] int64, their row in the [me_rows = L * B * Q][256] mask embeddings, -1 for a row whose
+ * assignment failed.  Row m = l * Ml + m_off[b] + j, so the host knows every row's image from L, B
+ * and n_b alone and passes `table` (int32, device): [img_off (B + 1) | order (M) | tiles (2 T)] --
+ * order = the rows grouped by image (image b owns order[img_off[b] .. img_off[b + 1]), layers
+ * ascending), tiles = (image, offset into order) of T row tiles of at most 32 entries of one image
+ * (kernel 1 only).  fp32 operands and accumulation on v_mfma_f32_32x32x2_f32, fixed summation
+ * order, no float atomics: the same inputs give the same bits.  Both write their whole output.  A
+ * row with mask_rows[m] < 0 contributes nothing and its G row is not read.  M <= 65535.
+ * ------------------------------------------------------------------------- */
+/* pixels per split-K slice of pn_mask_embed_grad_f32 (a constant: the slicing depends on P alone) */
+int pn_mask_grad_kslice(void);
+/* floats of pn_mask_embed_grad_f32's scratch: ceil(P / kslice) slices of [T * 32][256] */
+int64_t pn_mask_embed_grad_scratch_floats(int T, int64_t P);
+/* d mask_embed: dme[m][c] = sum_p G[m][p] * MF[b(m)][p][c], MF [B][P][256]; dme [M][256], a failed
+ * row comes out as exact zeros.  Per slice an ascending fmaf chain over its pixels, then the slices
+ * are added in ascending order. */
+int pn_mask_embed_grad_f32(const float* G, const float* MF, const int64_t* mask_rows,
+                           const int32_t* table, int64_t table_len, int M, int B, int T, int64_t P,
+                           float* scratch, int64_t scratch_floats, float* dme, void* stream);
+/* d mask_feature: dMF[b][p][c] = sum over image b's rows m (in `order`) of
+ * G[m][p] * me[mask_rows[m]][c]; dMF [B][P][256], zeros for an image without rows.  One ascending
+ * fmaf chain per element.  `tiles` is not read (table_len >= B + 1 + M). */
+int pn_mask_feature_grad_f32(const float* G, const float* me, const int64_t* mask_rows,
+                             const int32_t* table, int64_t table_len, int M, int B, int64_t P,
+                             int64_t me_rows, float* dMF, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

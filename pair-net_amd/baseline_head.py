@@ -44,6 +44,7 @@ class CrossHeadBaseline(CrossHead2):
         self._rel_loss_cfg = dict(train_cfg=kwargs.get("train_cfg"), rel_loss_cls=rel_loss_cls,
                                   sub_id_loss=sub_id_loss, obj_id_loss=obj_id_loss)
         self._rel_loss = None
+        self._seg_tape = None
         super().__init__(num_classes, in_channels, num_relations, num_obj_query=num_obj_query,
                          num_rel_query=num_rel_query, use_mask=use_mask, **kwargs)
 
@@ -210,6 +211,23 @@ class CrossHeadBaseline(CrossHead2):
                                        all_cls_scores["object_scores"], gt_rels_list,
                                        self._seg_loss.last["matched"], B, grads=grads, num_gts=G))
         return out
+
+    # ------------------------------------------------------- segmentation backward
+    def seg_backward(self, grads, pl=None):
+        """`grads` of `seg_losses` / `full_losses` carried back through the class / mask heads and
+        the nine masked decoder layers (seg_grad.py) -> (dmem [B, SN, 256], dMF [B, H2 * W2, 256],
+        {reference parameter name: gradient}).  Needs the plan of a `return_all_layers=True`
+        forward (default: the last one); the tape is built on first use."""
+        pl = pl if pl is not None else getattr(self, "_last_plan", None)
+        if pl is None or not getattr(pl, "all_layers", False):
+            raise RuntimeError("seg_backward needs a forward with return_all_layers=True")
+        if self._seg_loss is None or self._seg_loss.last is None:
+            raise RuntimeError("seg_backward needs the grads of a seg_losses / full_losses call")
+        if self._seg_tape is None:
+            from .seg_grad import SegmenterHeadGrad
+            self._seg_tape = SegmenterHeadGrad(self)
+        self._seg_tape.forward_from_plan(pl)
+        return self._seg_tape.backward(grads, counts=self._seg_loss.last["counts"])
 
     def seg_status(self):
         return None if self._seg_loss is None else self._seg_loss.assign_status

@@ -240,6 +240,12 @@ _SIGS = {
                                  _vp, _vp, _vp, _vp]),
     "pn_id_ce_f32": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _f32, _vp,
                                _vp, _vp, _vp, _vp]),
+    "pn_mask_grad_kslice": (C.c_int, []),
+    "pn_mask_embed_grad_scratch_floats": (_i64, [_i32, _i64]),
+    "pn_mask_embed_grad_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _i64,
+                                         _vp, _vp]),
+    "pn_mask_feature_grad_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _vp,
+                                           _vp]),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 34  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
@@ -1817,3 +1823,92 @@ def id_ce(sub, obj, matched, tab, pos, w_s, w_o, row_loss, out, g_sub=None, g_ob
                               _ptr(tab, torch.int64), _ptr(pos, torch.int32), pos.shape[0], B, R, Q,
                               w_s, w_o, _ptr(row_loss), _ptr(out), _ptr(g_sub), _ptr(g_obj),
                               _stream()), "pn_id_ce_f32")
+
+
+# ---- the mask logits' backward (csrc/seg_grad.hip; composed in seg_grad.py) -----------------------
+MASK_GRAD_MAX_ROWS = 65535
+MASK_GRAD_KSLICE = 2048   # pn_mask_grad_kslice(): pixels per split-K slice, a function of P alone
+
+
+def mask_grad_table(L, counts):
+    """The host table of the two mask-gradient kernels, from shapes alone: `counts` = n_b =
+    min(Q, G_b) per image, compact row m = l * sum(counts) + (rows of the images before b) + j.
+    -> (int32 host tensor [img_off (B + 1) | order (M) | tiles (2 T)], T): `order` groups the rows
+    by image (layers ascending), `tiles` are (image, offset into order) of the 32-row tiles of
+    pn_mask_embed_grad_f32, none of which crosses an image."""
+    L, counts = int(L), [int(c) for c in counts]
+    if L <= 0 or not counts or min(counts) < 0:
+        raise ValueError("L >= 1 layers and one non-negative row count per image")
+    Ml = sum(counts)
+    if L * Ml > MASK_GRAD_MAX_ROWS:
+        raise ValueError("at most %d matched rows per call, got %d" % (MASK_GRAD_MAX_ROWS, L * Ml))
+    img_off, order, tiles, m_off = [0], [], [], 0
+    for b, n in enumerate(counts):
+        order += [l * Ml + m_off + j for l in range(L) for j in range(n)]
+        tiles += [v for s in range(img_off[-1], len(order), 32) for v in (b, s)]
+        img_off.append(len(order))
+        m_off += n
+    return torch.tensor(img_off + order + tiles, dtype=torch.int32), len(tiles) // 2
+
+
+def _mask_grad_args(G, mask_rows, table, B, T):
+    if G.dim() != 2 or not G.is_contiguous():
+        raise ValueError("G: contiguous [M, h * w], got %s" % (tuple(G.shape),))
+    M, P = G.shape
+    if M > MASK_GRAD_MAX_ROWS:
+        raise ValueError("at most %d matched rows per call, got %d" % (MASK_GRAD_MAX_ROWS, M))
+    if P <= 0:
+        raise ValueError("G: no pixels")
+    if mask_rows.dim() != 1 or mask_rows.shape[0] != M or not mask_rows.is_contiguous():
+        raise ValueError("mask_rows: contiguous [%d], got %s" % (M, tuple(mask_rows.shape)))
+    if table.dim() != 1 or not table.is_contiguous() or table.numel() != B + 1 + M + 2 * T:
+        raise ValueError("table: %d + 1 + %d + 2 * %d int32 entries (mask_grad_table), got %d"
+                         % (B, M, T, table.numel()))
+    return M, P
+
+
+def mask_embed_grad_scratch_floats(T, P):
+    return int(lib().pn_mask_embed_grad_scratch_floats(int(T), int(P)))
+
+
+def mask_embed_grad(G, MF, mask_rows, table, T, dme, scratch):
+    """dme [M, 256] = G [M, P] x MF [B, P, 256] per image (include/pairnet_hip.h); `table`, `T`:
+    `mask_grad_table` on the device; scratch: `mask_embed_grad_scratch_floats(T, P)` floats.
+    Every row of dme is written (failed rows: zeros)."""
+    if MF.dim() != 3 or MF.shape[2] != 256 or not MF.is_contiguous():
+        raise ValueError("MF: contiguous [B, h * w, 256], got %s" % (tuple(MF.shape),))
+    B = MF.shape[0]
+    M, P = _mask_grad_args(G, mask_rows, table, B, T)
+    if MF.shape[1] != P:
+        raise ValueError("G has %d pixels per row, MF %d" % (P, MF.shape[1]))
+    if tuple(dme.shape) != (M, 256) or not dme.is_contiguous():
+        raise ValueError("dme: contiguous [%d, 256], got %s" % (M, tuple(dme.shape)))
+    need = mask_embed_grad_scratch_floats(T, P)
+    if M and (scratch is None or not scratch.is_contiguous() or scratch.numel() < need):
+        raise ValueError("scratch: %d floats (mask_embed_grad_scratch_floats)" % need)
+    _check(lib().pn_mask_embed_grad_f32(_ptr(G) if M else None, _ptr(MF),
+                                        _ptr(mask_rows, torch.int64) if M else None,
+                                        _ptr(table, torch.int32), table.numel(), M, B, T, P,
+                                        _ptr(scratch) if M else None,
+                                        scratch.numel() if M else 0, _ptr(dme) if M else None,
+                                        _stream()), "pn_mask_embed_grad_f32")
+
+
+def mask_feature_grad(G, me, mask_rows, table, T, dMF):
+    """dMF [B, P, 256] = sum over the image's rows of G[m]^T x me[mask_rows[m]]
+    (include/pairnet_hip.h); me [L * B * Q, 256].  Every element of dMF is written."""
+    if dMF.dim() != 3 or dMF.shape[2] != 256 or not dMF.is_contiguous():
+        raise ValueError("dMF: contiguous [B, h * w, 256], got %s" % (tuple(dMF.shape),))
+    B = dMF.shape[0]
+    if G.dim() == 2 and G.shape[0] == 0:            # no matched row at all: zeros
+        G = G.new_empty(0, dMF.shape[1])
+    M, P = _mask_grad_args(G, mask_rows, table, B, T)
+    if dMF.shape[1] != P:
+        raise ValueError("G has %d pixels per row, dMF %d" % (P, dMF.shape[1]))
+    if me.dim() != 2 or me.shape[1] != 256 or not me.is_contiguous():
+        raise ValueError("me: contiguous [L * B * Q, 256], got %s" % (tuple(me.shape),))
+    _check(lib().pn_mask_feature_grad_f32(_ptr(G) if M else None, _ptr(me),
+                                          _ptr(mask_rows, torch.int64) if M else None,
+                                          _ptr(table, torch.int32), table.numel(), M, B, P,
+                                          me.shape[0], _ptr(dMF), _stream()),
+           "pn_mask_feature_grad_f32")

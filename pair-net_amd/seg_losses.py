@@ -8,8 +8,9 @@ grid per batch, prepared as for `CrossHead2` by `PSGTr._prepare_gt_masks`; `Half
 accepted) -- and returns the same dict
 (`loss_cls`, `loss_mask`, `loss_dice`, `d0.loss_cls`, ..., the last layer unprefixed, :340-353) as
 0-dim device tensors: the VALUES and, with `grads={}`, the gradient of the SUM of the 3L terms with
-respect to the two logit stacks.  Carrying those gradients on through `mask_embed`, `cls_embed`, the
-mask feature, the FPN and the decoder is not built.
+respect to the two logit stacks.  `SegmenterHeadGrad` (seg_grad.py) carries those gradients on through
+`mask_embed`, `cls_embed`, `post_norm` and the nine masked decoder layers, to the mask feature and the
+memory tokens; the FPN side behind the mask feature is not built.
 
 Per layer and image (panoptic_heads/mask2former_head.py:157-221): `num_points` points shared by all
 maps, `pn_point_sample_f32` on predictions and ground truth, `pn_mask_match_cost_f32`, then ALL L * B
@@ -142,7 +143,8 @@ class Mask2FormerLoss:
         every key is optional, a missing one is drawn here.  `grads`: a dict filled with "cls"
         [L, B, Q, C + 1], "mask_rows" int64 [M] (row index into L * B * Q; -1 for a row whose
         assignment failed) and "mask" [M, h, w].  `self.last` keeps the call's targets (labels,
-        matched, mcount); `debug=True` also keeps its points, keys, candidates, samples and
+        matched, mcount) and `counts`, the host list n_b = min(Q, G_b) of matched rows per image
+        (what `SegmenterHeadGrad.backward` needs to know the rows' images); `debug=True` also keeps its points, keys, candidates, samples and
         coefficients alive there (hundreds of MB at production shapes)."""
         cls = all_cls_scores if torch.is_tensor(all_cls_scores) else torch.stack(list(all_cls_scores))
         mask = all_mask_preds if torch.is_tensor(all_mask_preds) else torch.stack(list(all_mask_preds))
@@ -256,7 +258,7 @@ class Mask2FormerLoss:
             hip.ce_avg_grad(cls3, labels, self._cw, g_cls.view(L, B * Q, C1), self.w_cls)
 
         # ---- loss_mask / loss_dice over the matched masks' loss points ----
-        self.last = dict(labels=labels, matched=matched, mcount=mcount)
+        self.last = dict(labels=labels, matched=matched, mcount=mcount, counts=list(n_b))
         if debug:
             self.last.update(assign=assign_pts, rows=rows, cols=cols, lsa_status=lsa_status)
         maps = mask.view(L * B * Q, h, w)
