@@ -48,7 +48,11 @@ def _rel_err(head_o, head, cls, ref_rel, ref_idx, trace_q):
     return _err(cls["rel"], rel), False
 
 
-def test_e2e_small_against_reference_golden():
+@pytest.mark.parametrize("gemm_arithmetic", ["bf16x3", "fp32"])
+def test_e2e_small_against_reference_golden(gemm_arithmetic):
+    """Both encoder arithmetics: "bf16x3" (the default: csrc/gemm_s3.hip) and "fp32"
+    (`_encoder_fp32` with csrc/gemm_ln.hip -- the forward the training tape differentiates)."""
+    from pairnet_amd import hip
     fx = golden("e2e_small")
     head_o, sd, crc = oracle_head(int(fx["weight_seed"]), overrides_of(fx))
     assert crc == int(fx["weight_crc"])
@@ -57,15 +61,29 @@ def test_e2e_small_against_reference_golden():
     assert seeded.checksum(feats) == int(fx["feat_crc"])
     metas = [dict(img_shape=(H, W, 3), scale_factor=[2.0, 2.0, 2.0, 2.0])] * bs
     head = _hip_head(sd)
-    cls, masks = head.forward([f.to(DEV) for f in feats], metas)
-    torch.cuda.synchronize()
+    head.gemm_arithmetic = gemm_arithmetic            # before the first forward
+    timer = hip.KernelTimer()
+    hip.TIMER = timer
+    try:
+        cls, masks = head.forward([f.to(DEV) for f in feats], metas)
+        torch.cuda.synchronize()
+    finally:
+        hip.TIMER = None
+    if gemm_arithmetic == "fp32":
+        # the launches of this forward are `_encoder_fp32`'s: the plan was built for "fp32", every
+        # encoder layer ran its two row-owning GEMM + LayerNorm launches (k_gemm_rowln: only that
+        # path issues them) and nothing ran on the bf16x3 pipe
+        names = [r[0] for r in timer.records]
+        assert head.gemm_arithmetic == "fp32" and "fp32" in head._last_plan.graph_cfg
+        assert names.count("k_gemm_rowln") == 2 * head.num_enc_layers
+        assert not [n for n in names if n.startswith("k_gemm_s3")]
     trace = {}
     head_o.forward(feats, metas, trace=trace)
     errs = {k: _err(cls[k], fx["cls_" + k]) for k in ("cls", "importance")}
     errs["rel"], same = _rel_err(head_o, head, cls, fx["cls_rel"], fx["topk_idx"],
                                  trace["query_feat"])
     errs["mask"] = _err(masks["mask"], fx["mask_mask"])
-    print("e2e_small errors:", errs, "top-k identical:", same)
+    print("e2e_small (%s) errors:" % gemm_arithmetic, errs, "top-k identical:", same)
     assert errs["rel"] < 1e-3 and errs["cls"] < 1e-3 and errs["importance"] < 1e-3
     assert errs["mask"] < 1e-3 * max(1.0, float(np.abs(fx["mask_mask"]).max()))
     pl = head._last_plan
