@@ -1317,6 +1317,34 @@ int pn_mask_feature_grad_f32(const float* G, const float* me, const int64_t* mas
                              const int32_t* table, int64_t table_len, int M, int B, int64_t P,
                              int64_t me_rows, float* dMF, void* stream);
 
+/* ---- backward of the pixel decoder's FPN branch (MSDeformAttnPixelDecoder.forward behind
+ * pairnet_head.py:262: lateral_convs.0 -> + bilinear-up(finest memory) -> output_convs.0 ->
+ * mask_feature; pair-net_amd/seg_grad.py SegPixelDecoderGrad).  No float atomics: bitwise
+ * reproducible. ---- */
+/* Adjoint of pn_bilinear_nhwc_f32 for an UPsampling (ho >= hi, wo >= wi; equal sizes: identity):
+ *   din[b][i][:] = (accumulate ? din : 0) + sum_o T[o][i] dout[b][o][:],
+ * T the forward's own fp32 tap matrix (the same make_tap per fine row / column; at the clamped
+ * last index both taps land on one coarse pixel and both are added).  dout [b][ho][wo][C] at
+ * dout + b*dout_bstride, din [b][hi][wi][C] at din + b*din_bstride (floats, multiples of 4);
+ * C % 4 == 0.  Gather form: per coarse element an fmaf chain over its fine columns (ascending)
+ * inside each fine row, then one fmaf per fine row (ascending). */
+int pn_bilinear_nhwc_bwd_f32(const float* dout, float* din, int B, int hi, int wi, int ho, int wo,
+                             int C, int accumulate, int64_t dout_bstride, int64_t din_bstride,
+                             void* stream);
+/* Backward of pn_groupnorm_nhwc_f32 (+ReLU) from its input x on the forward's row blocking, for
+ * the H/4 x W/4 map of the same branch (ConvModule norm + act of lateral_convs.0 / output_convs.0):
+ * with gate = relu ? (y > 0) : 1, y the saved output [B][HW][256] (dense; not read without relu),
+ *   dx [B][HW][256] (dense) = rstd (gamma dy gate - m1 - xhat m2),
+ *   dgamma[c] (+)= sum dy gate xhat,  dbeta[c] (+)= sum dy gate   (`accumulate`: add into them).
+ * stats: B * G * 4 floats out (mean, rstd, m1, m2); partials: B * nblk * G * 4 doubles and
+ * colpart: B * nblk * 512 floats of scratch, nblk = pn_groupnorm_nblk(HW); x / dy images start at
+ * multiples of x_bstride / dy_bstride floats.  C == 256, G <= 32, (256 / G) % 4 == 0. */
+int pn_groupnorm_act_nhwc_bwd_f32(const float* x, const float* dy, const float* y,
+                                  const float* gamma, float* dx, float* dgamma, float* dbeta,
+                                  float* stats, double* partials, float* colpart, int B, int64_t HW,
+                                  int G, float eps, int relu, int accumulate, int64_t x_bstride,
+                                  int64_t dy_bstride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,7 @@ class CrossHeadBaseline(CrossHead2):
                                   sub_id_loss=sub_id_loss, obj_id_loss=obj_id_loss)
         self._rel_loss = None
         self._seg_tape = None
+        self._segpd_tape = None
         super().__init__(num_classes, in_channels, num_relations, num_obj_query=num_obj_query,
                          num_rel_query=num_rel_query, use_mask=use_mask, **kwargs)
 
@@ -228,6 +229,28 @@ class CrossHeadBaseline(CrossHead2):
             self._seg_tape = SegmenterHeadGrad(self)
         self._seg_tape.forward_from_plan(pl)
         return self._seg_tape.backward(grads, counts=self._seg_loss.last["counts"])
+
+    def segmenter_backward(self, grads, feats, pl=None, need_dc2=False):
+        """`seg_backward(grads, pl)`, then its (dmem, dMF) on through the pixel decoder, FPN branch
+        included (`SegPixelDecoderGrad`, whose forward runs on `feats`, the backbone pyramid the
+        plan's forward saw) -> (dfeats, {reference parameter name: gradient}): dfeats = [d C5, d C4,
+        d C3, d C2 or None without `need_dc2`], the dict is the union of the trunk's and the pixel
+        decoder's.  The tape is built on first use and kept.
+
+        Known limitation: as in `TailTrainer`, the pixel decoder's tape runs its own exact-fp32
+        forward while the plan ran the encoder in `gemm_arithmetic`, so the two halves are
+        differentiated at operating points a few 1e-6 apart; nothing has measured what that
+        difference does to the gradients."""
+        dmem, dMF, g_trunk = self.seg_backward(grads, pl)
+        if self._segpd_tape is None:
+            from .seg_grad import SegPixelDecoderGrad
+            self._segpd_tape = SegPixelDecoderGrad(self)
+        self._segpd_tape.forward(feats)
+        dfeats, g_pd = self._segpd_tape.backward(dmem, dMF, need_dc2=need_dc2)
+        assert not set(g_trunk) & set(g_pd)
+        out = dict(g_trunk)
+        out.update(g_pd)
+        return dfeats, out
 
     def seg_status(self):
         return None if self._seg_loss is None else self._seg_loss.assign_status

@@ -246,6 +246,9 @@ _SIGS = {
                                          _vp, _vp]),
     "pn_mask_feature_grad_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _vp,
                                            _vp]),
+    "pn_bilinear_nhwc_bwd_f32": (C.c_int, [_vp, _vp] + [_i32] * 7 + [_i64, _i64, _vp]),
+    "pn_groupnorm_act_nhwc_bwd_f32": (C.c_int, [_vp] * 10 + [_i32, _i64, _i32, _f32, _i32, _i32,
+                                                             _i64, _i64, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 34  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
@@ -1496,6 +1499,37 @@ def groupnorm_nhwc_bwd(x, dy, gamma, dx, gxhat, stats, B, HW, G, x_bstride, dy_b
     _check(lib().pn_groupnorm_nhwc_bwd_f32(_ptr(x), _ptr(dy), _ptr(gamma), _ptr(dx), _ptr(gxhat),
                                            _ptr(stats), B, HW, G, eps, x_bstride, dy_bstride,
                                            _stream()), "pn_groupnorm_nhwc_bwd_f32")
+
+
+def bilinear_nhwc_bwd(dout, din, B, hi, wi, ho, wo, Cc, accumulate, dout_bstride, din_bstride):
+    """Adjoint of `bilinear_nhwc` (an upsampling): din [B][hi*wi][Cc] (+)= T^T dout [B][ho*wo][Cc]."""
+    _check(lib().pn_bilinear_nhwc_bwd_f32(_ptr(dout), _ptr(din), B, hi, wi, ho, wo, Cc,
+                                          int(accumulate), dout_bstride, din_bstride, _stream()),
+           "pn_bilinear_nhwc_bwd_f32")
+
+
+def groupnorm_act_bwd_scratch(B, HW, G, device):
+    """(partials, colpart) of `groupnorm_act_nhwc_bwd` for B images of HW pixels."""
+    nblk = groupnorm_nblk(HW)
+    return (torch.empty(B * nblk * G * 4, device=device, dtype=torch.float64),
+            torch.empty(B * nblk * 512, device=device, dtype=torch.float32))
+
+
+def groupnorm_act_nhwc_bwd(x, dy, y, gamma, dx, dgamma, dbeta, stats, scratch, B, HW, G, relu,
+                           accumulate, x_bstride, dy_bstride, eps=1e-5):
+    """GroupNorm (+ReLU, gate from the saved output `y`) backward on the forward's row blocking;
+    `scratch` from `groupnorm_act_bwd_scratch`; d gamma / d beta written or, with `accumulate`,
+    added into."""
+    partials, colpart = scratch
+    nblk = groupnorm_nblk(HW)
+    assert partials.numel() >= B * nblk * G * 4 and colpart.numel() >= B * nblk * 512
+    assert dx.is_contiguous() and dx.numel() == B * HW * 256 and stats.numel() >= B * G * 4
+    assert y is None or (y.is_contiguous() and y.numel() == B * HW * 256)
+    assert dgamma.is_contiguous() and dbeta.is_contiguous() and dgamma.numel() == dbeta.numel() == 256
+    _check(lib().pn_groupnorm_act_nhwc_bwd_f32(
+        _ptr(x), _ptr(dy), _ptr(y), _ptr(gamma), _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(stats),
+        _ptr(partials, torch.float64), _ptr(colpart), B, HW, G, eps, int(relu), int(accumulate),
+        x_bstride, dy_bstride, _stream()), "pn_groupnorm_act_nhwc_bwd_f32")
 
 
 def conv_wgrad(dY, X, part, B, Hi, Wi, Ho, Wo, Ci, Co, K, stride, pad, rows_per):

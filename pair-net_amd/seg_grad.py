@@ -20,16 +20,20 @@ LayerNorm / decoder-layer backward with the per-layer gradient added in after ea
 The boolean attention masks are `detach()`ed in the reference (:256): no gradient flows through
 them, and the heads' evaluation on the initial queries feeds only a mask, so it gets none.
 
-Not carried further here: dMF into the mask-feature convolution and the FPN, dmem into the pixel
-decoder (`PixelDecoderGrad.backward` takes it), the relation branch, `reduce_mean` across ranks, an
-optimizer step.
+`SegPixelDecoderGrad` takes both tensors on: dMF through `mask_feature`, `output_convs.0`,
+`lateral_convs.0` and the bilinear upsampling of the finest memory level (whose adjoint adds a
+second share to dmem), then `PixelDecoderGrad`'s walk through the encoder and the input
+convolutions on the sum.
+
+Not carried further here: the backbone below the feature gradients (`BackboneGrad` takes them), the
+relation branch, `reduce_mean` across ranks, an optimizer step.
 """
 import torch
 
 from . import hip
-from .grad import HeadGrad, RelationTailGrad
+from .grad import HeadGrad, PixelDecoderGrad, RelationTailGrad
 
-__all__ = ["SegmenterHeadGrad"]
+__all__ = ["SegmenterHeadGrad", "SegPixelDecoderGrad"]
 
 
 class SegmenterHeadGrad(HeadGrad):
@@ -250,3 +254,180 @@ class SegmenterHeadGrad(HeadGrad):
         ready(self.group_end["query"])
         ready(self.flat_numel)
         return dmem, dMF, grads_out
+
+
+class SegPixelDecoderGrad(PixelDecoderGrad):
+    """`PixelDecoderGrad` plus the mask-feature branch the segmentation losses reach
+    (MSDeformAttnPixelDecoder.forward behind pairnet_head.py:262: `lateral_convs.0` on C2, + the
+    bilinear upsampling of the finest memory level, `output_convs.0`, `mask_feature`):
+
+        tape = SegPixelDecoderGrad(head)
+        mem, MF = tape.forward(feats)                      # MF [B, H2 * W2, 256]
+        dfeats, grads = tape.backward(dmem, dMF, need_dc2=False)
+
+    `dmem`, `dMF`: what `SegmenterHeadGrad.backward` returns.  `dfeats[0..2]` are the parent's (C5,
+    C4, C3), `dfeats[3]` is d C2 [B, C, H2, W2] or None without `need_dc2` (the R50 config freezes
+    layer1).  The upsampling's adjoint (`pn_bilinear_nhwc_bwd_f32`) adds the branch's share into the
+    level-2 rows of a copy of `dmem`, and the parent's walk runs on that sum.  The 3x3 convolution
+    is taped as the direct implicit GEMM (as `BackboneGrad` does), its data gradient is the forward
+    convolution on the tap-reversed weight (`dgrad_algo`: Winograd F(4x4, 3x3), the faster form at
+    200 x 334, or the direct kernel), its weight gradient `pn_conv_wgrad_f32`; the two GroupNorms go
+    back through `pn_groupnorm_act_nhwc_bwd_f32` (the ReLU's gate from the saved output).  The three
+    new parameter groups come first in the flat buffer, in completion order.
+
+    The branch's own results -- its eight gradients, d C2 and `self.dmem_sum`, the sum handed to
+    the parent -- are bitwise reproducible.  The parent's walk is not, from the first
+    `pn_msda_bwd_f32` on: that kernel adds grad_value with float atomics, like mmcv's
+    (csrc/msda.hip), so everything behind layer 5's `value_proj` varies in its last bits from
+    call to call, as `PixelDecoderGrad.backward`'s results always have."""
+
+    BRANCH_GROUPS = [
+        ("mask_feature", [PixelDecoderGrad.PD + "mask_feature." + n for n in ("weight", "bias")]),
+        ("output_convs.0", [PixelDecoderGrad.PD + "output_convs.0." + n
+                            for n in ("conv.weight", "gn.weight", "gn.bias")]),
+        ("lateral_convs.0", [PixelDecoderGrad.PD + "lateral_convs.0." + n
+                             for n in ("conv.weight", "gn.weight", "gn.bias")])]
+
+    def __init__(self, head, flat=None, base=0):
+        super().__init__(head, flat, base)
+        self._zeroed = False
+        self.dgrad_algo = "winograd4"   # the 3x3's data gradient: "winograd4" or "direct"
+
+    @staticmethod
+    def param_groups(head):
+        return list(SegPixelDecoderGrad.BRANCH_GROUPS) + PixelDecoderGrad.param_groups(head)
+
+    def _zero_grads(self):
+        if not self._zeroed:            # (the parent's walk runs inside backward(): zeroed once)
+            self.flat_grad.zero_()
+        return self.grads
+
+    # ------------------------------------------------------------------ forward with a tape
+    @torch.no_grad()
+    @hip.on_device
+    def forward(self, feats):
+        mem = PixelDecoderGrad.forward(self, feats)
+        head, w, E, pd, t = self.head, self.head.w, self._E, self.PD, self.t
+        B, SN, start = t["B"], t["SN"], t["start"]
+        f = feats[0]
+        cin, (H2, W2) = f.shape[1], f.shape[-2:]
+        HW2, G = H2 * W2, head.gn_groups
+        h2, w2 = t["shapes"][2]
+        part = torch.empty(B * hip.groupnorm_nblk(HW2) * G * 2, device=self.dev,
+                           dtype=torch.float64)
+        rows = [self._rows(f[b]) for b in range(B)]
+        lat = E(B, HW2, 256)
+        for b in range(B):
+            hip.linear(rows[b], w[pd + "lateral_convs.0.conv.weight"], None, lat[b])
+        T = E(B, H2, W2, 256)
+        hip.groupnorm_nhwc(lat, w[pd + "lateral_convs.0.gn.weight"],
+                           w[pd + "lateral_convs.0.gn.bias"], T, part, B, HW2, G, False,
+                           HW2 * 256, HW2 * 256)
+        hip.bilinear_nhwc(mem[:, start[2]:], T, B, h2, w2, H2, W2, 256, True, SN * 256, HW2 * 256)
+        c3 = E(B, H2, W2, 256)
+        hip.conv2d_ex(T, w[pd + "output_convs.0.conv.weight"], None, None, c3, B, H2, W2, 256, 256,
+                      3, 3, 1, 1)
+        Y = E(B, H2, W2, 256)
+        hip.groupnorm_nhwc(c3, w[pd + "output_convs.0.gn.weight"], w[pd + "output_convs.0.gn.bias"],
+                           Y, part, B, HW2, G, True, HW2 * 256, HW2 * 256)
+        MF = E(B, HW2, 256)
+        hip.linear(Y.view(-1, 256), w[pd + "mask_feature.weight"], w[pd + "mask_feature.bias"],
+                   MF.view(-1, 256))
+        t["fpn"] = dict(rows=rows, lat=lat, T=T, c3=c3, Y=Y, hw2=(H2, W2), cin=cin)
+        return mem, MF
+
+    # ------------------------------------------------------------------ backward
+    def _gn_bwd(self, x, dy, y, prefix, grads, B, HW, scratch, stats):
+        """GroupNorm (+ReLU when `y`, its saved output, is given) backward -> dx [B * HW, 256];
+        d weight / d bias accumulated."""
+        dx = self._E(B * HW, 256)
+        hip.groupnorm_act_nhwc_bwd(x, dy, y, self.head.w[prefix + "weight"], dx,
+                                   grads[prefix + "weight"], grads[prefix + "bias"], stats, scratch,
+                                   B, HW, self.head.gn_groups, y is not None, True, HW * 256,
+                                   HW * 256)
+        return dx
+
+    def _check_upstream(self, dmem, dMF):
+        t = self.t
+        B, SN = t["B"], t["SN"]
+        H2, W2 = t["fpn"]["hw2"]
+        if self.dgrad_algo not in ("winograd4", "direct"):
+            raise ValueError("dgrad_algo %r: 'winograd4' or 'direct'" % (self.dgrad_algo,))
+        for name, g, shape in (("dmem", dmem, (B, SN, 256)), ("dMF", dMF, (B, H2 * W2, 256))):
+            if not (torch.is_tensor(g) and g.is_cuda and g.device == self.dev and
+                    g.dtype == torch.float32):
+                raise ValueError("%s: an fp32 tensor on %s" % (name, self.dev))
+            if tuple(g.shape) != shape:
+                raise ValueError("%s %s does not match the tape's %s" % (name, tuple(g.shape), shape))
+        return dmem.contiguous(), dMF.contiguous()
+
+    @torch.no_grad()
+    @hip.on_device
+    def backward(self, dmem, dMF, need_dc2=False, on_ready=None):
+        if self.t is None or "fpn" not in self.t:
+            raise RuntimeError("backward() needs a forward() first")
+        dmem, dMF = self._check_upstream(dmem, dMF)
+        head, w, E, pd, t = self.head, self.head.w, self._E, self.PD, self.t
+        B, SN, start, s = t["B"], t["SN"], t["start"], t["fpn"]
+        (H2, W2), cin, G = s["hw2"], s["cin"], head.gn_groups
+        HW2 = H2 * W2
+        h2, w2 = t["shapes"][2]
+        ready = on_ready if on_ready is not None else (lambda end: None)
+        grads = self._zero_grads()
+        scratch = hip.groupnorm_act_bwd_scratch(B, HW2, G, self.dev)
+        stats = E(B * G * 4)
+        # ---- mask_feature (a linear layer over pixels) ----
+        dY = self._lin_bwd(dMF.view(-1, 256), s["Y"].view(-1, 256), w[pd + "mask_feature.weight"],
+                           grads, pd + "mask_feature.weight", pd + "mask_feature.bias")
+        ready(self.group_end["mask_feature"])
+        # ---- output_convs.0: GroupNorm + ReLU, then the 3x3 convolution ----
+        dc3 = self._gn_bwd(s["c3"], dY, s["Y"], pd + "output_convs.0.gn.", grads, B, HW2, scratch,
+                           stats)
+        del dY
+        rows_per = max(1, min(H2, 8))
+        chunks = B * ((H2 + rows_per - 1) // rows_per)
+        part = E(chunks, 256 * 9 * 256)
+        hip.conv_wgrad(dc3, s["T"], part, B, H2, W2, H2, W2, 256, 256, 3, 1, 1, rows_per)
+        dwp = E(256 * 9 * 256)                                # [co][tap][ci]: the packed layout
+        hip.colsum(part, dwp)
+        del part
+        grads[pd + "output_convs.0.conv.weight"].copy_(
+            dwp.view(256, 3, 3, 256).permute(0, 3, 1, 2))     # -> [co][ci][3][3]
+        ready(self.group_end["output_convs.0"])
+        wb = E(256 * 9 * 256)
+        hip.conv_weight_bwd_layout(w[pd + "output_convs.0.conv.weight"], wb, 256, 9, 256)
+        dT = E(B, H2, W2, 256)
+        if self.dgrad_algo == "winograd4":
+            # F(4x4, 3x3) on the reversed weight: 0.29 against 0.72 ms at 200 x 334 (labnotes R20.4)
+            U = hip.winograd43_weights(wb.view(256, 3, 3, 256).permute(0, 3, 1, 2).contiguous())
+            tiles = B * ((H2 + 3) // 4) * ((W2 + 3) // 4)
+            hip.conv3x3_winograd43(dc3, U, None, dT, E(36 * tiles * 256), E(36 * tiles * 256), B, H2,
+                                   W2, 256, 256, False)
+        elif self.dgrad_algo == "direct":
+            hip.conv2d_ex(dc3, wb.view(256, 9 * 256), None, None, dT, B, H2, W2, 256, 256, 3, 3, 1, 1)
+        else:
+            raise ValueError("dgrad_algo %r: 'winograd4' or 'direct'" % (self.dgrad_algo,))
+        del dc3
+        # ---- dT splits: lateral_convs.0 (GroupNorm, 1x1 convolution on C2) ... ----
+        dlat = self._gn_bwd(s["lat"], dT, None, pd + "lateral_convs.0.gn.", grads, B, HW2, scratch,
+                            stats)
+        dc2 = E(B, cin, H2, W2) if need_dc2 else None
+        for b in range(B):
+            drows = self._lin_bwd(dlat[b * HW2:(b + 1) * HW2], s["rows"][b],
+                                  w[pd + "lateral_convs.0.conv.weight"], grads,
+                                  pd + "lateral_convs.0.conv.weight", None, need_dx=need_dc2)
+            if need_dc2:
+                hip.transpose(drows, dc2[b].view(cin, HW2))
+        ready(self.group_end["lateral_convs.0"])
+        # ---- ... and the upsampling's adjoint into the finest level's rows of the memory ----
+        dsum = dmem.clone()
+        hip.bilinear_nhwc_bwd(dT, dsum[:, start[2]:], B, h2, w2, H2, W2, 256, True, HW2 * 256,
+                              SN * 256)
+        del dT
+        self.dmem_sum = dsum                    # what enters the parent's walk (dmem + the branch's share)
+        self._zeroed = True
+        try:
+            dfeats, grads = PixelDecoderGrad.backward(self, dsum, on_ready)
+        finally:
+            self._zeroed = False
+        return dfeats + [dc2], grads

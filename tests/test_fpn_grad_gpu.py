@@ -1,0 +1,295 @@
+"""GPU: `SegPixelDecoderGrad` (pair-net_amd/seg_grad.py) -- the segmentation-loss gradients carried
+from (dmem, dMF) through `mask_feature`, `output_convs.0`, `lateral_convs.0`, the upsampling's
+adjoint and `PixelDecoderGrad`'s walk -- against float64 autograd through the reference-pinned
+oracle's pixel decoder, the branch under the tape's own ReLU gate (tests/fpn_grad_ref.py `branch`).
+Tolerance: `_compare` / `_compare_params` of tests/test_grad_gpu.py at 1e-4 of each tensor's
+largest entry.  A seeded `CrossHeadBaseline` as tests/test_seg_grad_gpu.py builds it, on two
+pyramids: 64 x 96 (C2 16 x 24 over C3 8 x 12, exact 2x) and 52 x 76 (C2 13 x 19 over C3 7 x 10:
+an odd width for conv_wgrad's pixel pairs, a ragged last row chunk, a non-integer ratio)."""
+import pytest
+import torch
+
+import fpn_grad_ref as R
+from helpers import baseline_cfg, oracle_baseline_head
+from oracle import seeded
+from test_grad_gpu import _compare, _compare_params, _print
+from test_seg_grad_gpu import COUNTS, _oracle64, _train_cfg, _trunk_names
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+PYRAMIDS = [(64, 96), (52, 76)]
+_S = {}
+
+
+def _head():
+    if "head" not in _S:
+        assert torch.cuda.is_available(), "-m gpu tests need the MI355X"
+        from pairnet_amd import CrossHeadBaseline
+        _, sd, _ = oracle_baseline_head(1234)
+        head = CrossHeadBaseline(**baseline_cfg(), train_cfg=_train_cfg())
+        head.load_state_dict(sd)
+        head.to(DEV)
+        head.exact_mask_order = True
+        head.return_all_layers = True
+        _S["head"] = (head, sd)
+    return _S["head"]
+
+
+def _run(H, W):
+    """One inference forward and one taped forward per pyramid, with random upstream gradients."""
+    if (H, W) not in _S:
+        from pairnet_amd import SegPixelDecoderGrad
+        head, sd = _head()
+        feats = seeded.seeded_feats(99, 2, H, W)
+        dfe = [f.to(DEV) for f in feats]
+        metas = [dict(img_shape=(H, W, 3), scale_factor=[1.5] * 4)] * 2
+        cls, masks = head.forward(dfe, metas)
+        torch.cuda.synchronize()
+        pl = head._last_plan
+        tape = SegPixelDecoderGrad(head)
+        mem, MF = tape.forward(dfe)
+        torch.cuda.synchronize()
+        g = torch.Generator().manual_seed(H + W)
+        _S[(H, W)] = dict(feats=feats, dfe=dfe, pl=pl, plMF=pl.MF.view(2, pl.HW2, 256).clone(),
+                          plX=pl.X.clone(), cls=cls, masks=masks, tape=tape, mem=mem, MF=MF,
+                          G_mem=torch.randn(tuple(mem.shape), generator=g).to(DEV),
+                          G_MF=torch.randn(tuple(MF.shape), generator=g).to(DEV))
+    return _S[(H, W)]
+
+
+def _reference(H, W):
+    """Float64 autograd of <MF, G_MF> and of sum_l <outs_l, G_mem,l> through the oracle's pixel
+    decoder, separately (the functional is linear in the pair): -> dict(mem, MF: lists of the four
+    feature gradients + {parameter name: gradient}; z: the statement's pre-ReLU map)."""
+    key = ("ref", H, W)
+    if key not in _S:
+        head, sd = _head()
+        s = _run(H, W)
+        head_o = _oracle64(sd)
+        pd = head_o.pixel_decoder
+        f64 = [f.double().requires_grad_() for f in s["feats"]]
+        _, memories = pd(f64)
+        mem_ref = torch.cat([m.flatten(2).transpose(1, 2) for m in memories], 1)
+        Y = s["tape"].t["fpn"]["Y"]                                  # [B, H2, W2, 256], post-ReLU
+        gate = (Y > 0).permute(0, 3, 1, 2).cpu().double()
+        MFr, z = R.branch(f64[0], memories[2], R.branch_params(pd), head.gn_groups, gate=gate)
+        MFr = MFr.flatten(2).transpose(1, 2)                        # [B, H2 * W2, 256]
+        names = [n for n, _ in head_o.named_parameters() if n.startswith("pixel_decoder.")]
+        params = [dict(head_o.named_parameters())[n] for n in names]
+        out = dict(z=z.detach(), gate=gate, mem_val=mem_ref.detach(), MF_val=MFr.detach(),
+                   names=names, head_o=head_o)
+        for k, loss in (("mem", (mem_ref * s["G_mem"].cpu().double()).sum()),
+                        ("MF", (MFr * s["G_MF"].cpu().double()).sum())):
+            gs = torch.autograd.grad(loss, f64 + params, retain_graph=True, allow_unused=True)
+            out[k] = ([g for g in gs[:4]], dict(zip(names, gs[4:])))
+        _S[key] = out
+    return _S[key]
+
+
+def _sum(a, b):
+    if a is None or b is None:
+        return a if b is None else b
+    return a + b
+
+
+def _check(H, W, dfeats, grads, parts, report):
+    """`parts`: which of the reference's two halves the upstream gradients contained."""
+    ref = _reference(H, W)
+    fg, pg = [None] * 4, {n: None for n in ref["names"]}
+    for k in parts:
+        fg = [_sum(a, b) for a, b in zip(fg, ref[k][0])]
+        pg = {n: _sum(pg[n], ref[k][1][n]) for n in pg}
+    for l in range(3):
+        _compare("features of level %d" % l, dfeats[l], fg[3 - l], report)
+    _compare("features C2", dfeats[3], fg[0], report)
+    head_o = ref["head_o"]
+    for n, p in head_o.named_parameters():
+        p.grad = pg.get(n)
+    names = [n for n in ref["names"] if pg[n] is not None]
+    assert len(ref["names"]) == 117
+    _compare_params(grads, head_o, report, names)
+    return names
+
+
+@pytest.mark.parametrize("H,W", PYRAMIDS)
+def test_taped_forward_equals_the_plans(H, W):
+    s = _run(H, W)
+    e_mf = float((s["MF"] - s["plMF"]).abs().max())
+    e_mem = float((s["mem"] - s["plX"]).abs().max())
+    ref = _reference(H, W)
+    e_o = float((s["mem"].cpu().double() - ref["mem_val"]).abs().max())
+    print("taped forward %dx%d: MF vs plan %.2e, mem vs plan %.2e, mem vs oracle %.2e"
+          % (H, W, e_mf, e_mem, e_o))
+    assert s["MF"].shape == s["plMF"].shape and e_mf < 1e-4
+    assert e_o < 1e-4                                  # (as the parent's test holds `mem`)
+    # the ReLU-gate cap: a condition of the comparison below, not a measurement
+    frac = R.gate_mismatch(ref["gate"], ref["z"])
+    print("gate mismatch tape vs float64: %.3e (cap %.0e)" % (frac, R.GATE_CAP))
+    assert frac <= R.GATE_CAP
+    assert float((s["MF"].cpu().double() - ref["MF_val"]).abs().max()) < 1e-4
+
+
+@pytest.mark.parametrize("algo", ["winograd4", "direct"])
+@pytest.mark.parametrize("H,W", PYRAMIDS)
+def test_backward_against_float64_autograd(H, W, algo):
+    """Both forms of the 3x3's data gradient; "winograd4" is the default."""
+    s = _run(H, W)
+    tape = s["tape"]
+    assert tape.dgrad_algo == "winograd4"
+    ends = []
+    tape.dgrad_algo = algo
+    try:
+        dfeats, grads = tape.backward(s["G_mem"], s["G_MF"], need_dc2=True, on_ready=ends.append)
+    finally:
+        tape.dgrad_algo = "winograd4"
+    torch.cuda.synchronize()
+    report = []
+    names = _check(H, W, dfeats, grads, ("mem", "MF"), report)
+    assert len(names) == 117 and sorted(names) == sorted(grads)
+    _print(report)
+    # flat layout: views of one buffer in the reference's shapes, groups in completion order
+    lo = tape.flat_grad.data_ptr()
+    shapes = _head()[0].param_shapes()
+    for n, (off, shape, numel) in tape.layout.items():
+        assert grads[n].data_ptr() == lo + 4 * off and tuple(grads[n].shape) == shape == shapes[n]
+    assert ends == sorted(ends) and ends[-1] == tape.flat_numel == tape.size_of(_head()[0])
+    assert ends[:3] == [tape.group_end[g] for g in ("mask_feature", "output_convs.0",
+                                                    "lateral_convs.0")]
+
+
+def _same_walk(dfeats, grads, ref_dfeats, ref_grads, report):
+    """Two runs of `PixelDecoderGrad`'s walk on bitwise equal upstream gradients.  The walk is not
+    bitwise reproducible: `pn_msda_bwd_f32` adds grad_value with float atomics (csrc/msda.hip says
+    so; measured, labnotes R20.3: two calls of `PixelDecoderGrad.backward` on the same tensors
+    differ in every feature gradient).  What is finished before the first such sum -- the last
+    encoder layer's gradients except `value_proj` -- is compared bit for bit, the rest at this
+    file's tolerance."""
+    from pairnet_amd import PixelDecoderGrad
+    head, _ = _head()
+    last = dict(PixelDecoderGrad.param_groups(head))["encoder.layers.%d" % (head.num_enc_layers - 1)]
+    exact = [n for n in last if "value_proj" not in n]
+    assert len(exact) == 14
+    for n in ref_grads:
+        if n in exact:
+            assert torch.equal(grads[n], ref_grads[n]), n
+        elif n not in R.BRANCH_PARAMS:
+            _compare(n, grads[n], ref_grads[n], report)
+    for l in range(3):
+        _compare("features of level %d" % l, dfeats[l], ref_dfeats[l], report)
+
+
+def test_zero_mask_feature_gradient_is_the_parents_backward():
+    """The issue asks for bitwise equality with `PixelDecoderGrad.backward(G_mem)` throughout; that
+    cannot hold for the parent against itself (`_same_walk`).  Held bitwise: the tensor handed to
+    the parent's walk equals G_mem, the eight new gradients and d C2 are exact zeros, and the
+    parent's gradients in front of the atomics; the rest at 1e-4 of each tensor's largest entry."""
+    from pairnet_amd import PixelDecoderGrad
+    H, W = PYRAMIDS[0]
+    s = _run(H, W)
+    head, _ = _head()
+    parent = PixelDecoderGrad(head)
+    parent.forward(s["dfe"])
+    pf, pg = parent.backward(s["G_mem"])
+    tape = s["tape"]
+    dfeats, grads = tape.backward(s["G_mem"], torch.zeros_like(s["G_MF"]), need_dc2=True)
+    torch.cuda.synchronize()
+    assert torch.equal(tape.dmem_sum, s["G_mem"])
+    report = []
+    _same_walk(dfeats, grads, pf, pg, report)
+    _print(report)
+    assert sorted(set(grads) - set(pg)) == sorted(R.BRANCH_PARAMS)
+    for n in R.BRANCH_PARAMS:
+        assert float(grads[n].abs().max()) == 0.0, n
+    assert float(dfeats[3].abs().max()) == 0.0
+
+
+def test_zero_memory_gradient_reaches_the_coarse_levels_through_the_encoder():
+    H, W = PYRAMIDS[0]
+    s = _run(H, W)
+    dfeats, grads = s["tape"].backward(torch.zeros_like(s["G_mem"]), s["G_MF"], need_dc2=True)
+    torch.cuda.synchronize()
+    report = []
+    _check(H, W, dfeats, grads, ("MF",), report)
+    _print(report)
+    assert float(dfeats[0].abs().max()) > 0 and float(dfeats[1].abs().max()) > 0
+
+
+def test_without_dc2_everything_else_is_unchanged():
+    """Bitwise: the branch's gradients and the sum handed to the parent's walk; the walk itself as
+    `_same_walk` holds it."""
+    H, W = PYRAMIDS[1]
+    s = _run(H, W)
+    tape = s["tape"]
+    dfeats, grads = tape.backward(s["G_mem"], s["G_MF"], need_dc2=True)
+    keep = ([d.clone() for d in dfeats], {k: v.clone() for k, v in grads.items()},
+            tape.dmem_sum.clone())
+    dfeats2, grads2 = tape.backward(s["G_mem"], s["G_MF"])
+    torch.cuda.synchronize()
+    assert dfeats2[3] is None and len(dfeats2) == 4 and sorted(grads2) == sorted(keep[1])
+    assert torch.equal(tape.dmem_sum, keep[2])
+    for n in R.BRANCH_PARAMS:
+        assert torch.equal(grads2[n], keep[1][n]), n
+    report = []
+    _same_walk(dfeats2, grads2, keep[0], keep[1], report)
+    _print(report)
+
+
+def test_segmenter_backward_is_the_manual_composition():
+    from pairnet_amd import SegPixelDecoderGrad
+    H, W = PYRAMIDS[0]
+    s = _run(H, W)
+    head, _ = _head()
+    metas = [dict(img_shape=(H, W, 3), scale_factor=[1.5] * 4)] * 2
+    cls, masks = head.forward(s["dfe"], metas)              # (a fresh plan state for this pyramid)
+    pl = head._last_plan
+    gen = torch.Generator().manual_seed(8)
+    gt_labels = [torch.randint(0, 133, (n,), generator=gen) for n in COUNTS]
+    gt_masks = [(torch.rand(n, 32, 48, generator=gen) > 0.6).to(torch.uint8) for n in COUNTS]
+    grads = {}
+    head.seg_losses(cls, masks, gt_labels, gt_masks, [dict()] * 2, grads=grads, seed=3)
+    dfeats, g = head.segmenter_backward(grads, s["dfe"], need_dc2=True)
+    torch.cuda.synchronize()
+    got = ([d.clone() for d in dfeats], {k: v.clone() for k, v in g.items()})
+    dmem, dMF, g_trunk = head.seg_backward(grads, pl)
+    tape = SegPixelDecoderGrad(head)
+    tape.forward(s["dfe"])
+    df2, g_pd = tape.backward(dmem, dMF, need_dc2=True)
+    torch.cuda.synchronize()
+    both = dict(g_trunk)
+    both.update(g_pd)
+    assert sorted(got[1]) == sorted(both) == sorted(_trunk_names() + list(tape.layout))
+    assert len(tape.layout) == 117 and len(got[1]) == len(_trunk_names()) + 117
+    # bitwise: the trunk, the branch (d C2 included) and the sum handed to the parent's walk; the
+    # walk itself as `_same_walk` holds it
+    for k in list(g_trunk) + R.BRANCH_PARAMS:
+        assert torch.equal(got[1][k], both[k]), k
+    assert torch.equal(got[0][3], df2[3]) and torch.equal(head._segpd_tape.dmem_sum, tape.dmem_sum)
+    report = []
+    _same_walk(got[0], got[1], df2, g_pd, report)
+    _print(report)
+    assert float(got[1]["pixel_decoder.mask_feature.weight"].abs().max()) > 0
+    assert head.segmenter_backward(grads, s["dfe"], pl=pl)[0][3] is None
+    # what seg_backward and the tape refuse, this refuses
+    with pytest.raises(ValueError):
+        head.segmenter_backward({k: v for k, v in grads.items() if k != "mask"}, s["dfe"])
+    with pytest.raises((ValueError, RuntimeError, AssertionError)):
+        head.segmenter_backward(grads, [f[:1] for f in s["dfe"]])    # another batch than the plan's
+
+
+def test_refusals():
+    from pairnet_amd import CrossHeadBaseline, SegPixelDecoderGrad
+    H, W = PYRAMIDS[0]
+    s = _run(H, W)
+    head, _ = _head()
+    with pytest.raises(RuntimeError):
+        SegPixelDecoderGrad(CrossHeadBaseline(**baseline_cfg()))       # not on the device
+    with pytest.raises(RuntimeError):
+        SegPixelDecoderGrad(head).backward(s["G_mem"], s["G_MF"])      # before forward
+    tape, dm, dF = s["tape"], s["G_mem"], s["G_MF"]
+    keep = tape.flat_grad.clone()
+    for bad in ((dm[:, :-1], dF), (dm, dF[:, :-1]), (dm[:1], dF[:1]), (dm.double(), dF),
+                (dm, dF.double()), (dm.cpu(), dF), (dm, dF.cpu()), (dm, dF.view(2, -1)),
+                (None, dF)):
+        with pytest.raises(ValueError):
+            tape.backward(*bad)
+    assert torch.equal(tape.flat_grad, keep)                           # refused before any launch
