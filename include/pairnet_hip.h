@@ -46,7 +46,8 @@ int pn_abi_version(void);
  * ------------------------------------------------------------------------- */
 #define PN_GEMM_RELU       1   /* act = ReLU (else identity)                        */
 #define PN_GEMM_A_COLMAJOR 2   /* A is stored [K][lda] (an NCHW feature map)        */
-#define PN_GEMM_FORCE_TILE 4   /* testing: force the 128x128 tile of the LDS kernel */
+#define PN_GEMM_FORCE_TILE 4   /* testing: force the 128x128 tile of the LDS kernel (128x64
+                                * where aadd_from_col is an odd multiple of 64)      */
 #define PN_GEMM_FORCE_SKINNY 8 /* testing: force the 32x32 split-K-in-block kernel  */
 #define PN_GEMM_FORCE_TILE64 16     /* tuning: 64x64 tile (row-major A)             */
 #define PN_GEMM_FORCE_TILE128x64 32 /* tuning: 128x64 tile                          */
@@ -84,7 +85,8 @@ int pn_gemm_f32(const pn_gemm_desc* d, void* stream);
 
 /* `count` (<= 18) independent row-major problems in ONE launch of the persistent 64x64
  * tile kernel (all their tiles share the grid): used for the 18 key/value projections of
- * the 9 decoder layers, whose per-problem tile counts do not fill 256 CUs evenly. */
+ * the 9 decoder layers, whose per-problem tile counts do not fill 256 CUs evenly.  Every problem
+ * needs K >= 32 (the tile kernel stages 32 columns of a row at a time); else PN_BAD_ARG. */
 int pn_gemm_group_f32(const pn_gemm_desc* d, int count, void* stream);
 
 /* Resident workgroups per CU the persistent 64x64-tile kernel (plain row-major A) is sized
@@ -144,10 +146,13 @@ int pn_winograd_f43_output_f32(const float* M, const float* bias, float* out, in
  * oracle/backbone.py).  BatchNorm is folded into the convolution weights / bias by the
  * caller; activations are channel-last.
  * ------------------------------------------------------------------------- */
-/* General form of the convolution above: stride >= 1, any padding,
+/* General form of the convolution above: stride >= 1, 0 <= 2 pad <= min(KH, KW) - 1 (a larger
+ * pad is refused with PN_BAD_ARG: the loader reads the pixel (oy stride, ox stride) in place of a
+ * tap outside the image, which must itself lie inside it),
  *   Ho = (H + 2 pad - KH) / stride + 1 (same for W),
  *   out = [relu_after](act(conv + bias) + res),  res/out [B][Ho][Wo][Cout],
- * flags: PN_GEMM_RELU (act), PN_GEMM_RELU_AFTER_RES, tile selectors, PN_GEMM_RESERVE(n). */
+ * flags: PN_GEMM_RELU (act), PN_GEMM_RELU_AFTER_RES, tile selectors, PN_GEMM_RESERVE(n),
+ * PN_GEMM_KSPLIT(n). */
 int pn_conv2d_nhwc_ex_f32(const float* in, const float* Wp, const float* bias,
                           const float* res, float* out, int B, int H, int W, int Cin,
                           int Cout, int KH, int KW, int stride, int pad, int flags,

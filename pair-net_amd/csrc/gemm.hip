@@ -990,12 +990,20 @@ static bool gemm_use_skinny(const pn_gemm_desc* d) {
   return skinny;
 }
 
+// A tile adds Aadd to its whole A panel or not at all (set_tile: n0 >= aadd_from_col), so a tile
+// must not straddle aadd_from_col (a multiple of 64): a forced 128x128 launch whose boundary is an
+// odd multiple of 64 runs as 128x64 tiles.
+static bool gemm_tile128_narrow(const pn_gemm_desc* d) {
+  return d->Aadd && d->aadd_from_col % 128 != 0;
+}
+
 extern "C" int pn_gemm_variant(const pn_gemm_desc* d) {
   if (!d || d->M <= 0 || d->N <= 0 || d->batch <= 0) return PN_BAD_ARG;
   const int col = (d->flags & PN_GEMM_A_COLMAJOR) ? 1 : 0;
   if (gemm_use_skinny(d)) return PN_GEMM_VARIANT_SKINNY + col;
   if (d->flags & PN_GEMM_FORCE_TILE128x64) return PN_GEMM_VARIANT_TILE_128x64 + col;
-  if (d->flags & PN_GEMM_FORCE_TILE) return PN_GEMM_VARIANT_TILE_128x128 + col;
+  if (d->flags & PN_GEMM_FORCE_TILE)
+    return (gemm_tile128_narrow(d) ? PN_GEMM_VARIANT_TILE_128x64 : PN_GEMM_VARIANT_TILE_128x128) + col;
   return PN_GEMM_VARIANT_TILE_64x64 + col;
 }
 
@@ -1041,7 +1049,8 @@ extern "C" int pn_gemm_f32(const pn_gemm_desc* d, void* stream) {
   // selectable for sweeps.
   const bool big_m = PN_GEMM_BIGM_128x64 && !colmajor && !d->Aadd && d->M >= 16384 &&
                      d->N >= 256 && d->N % 64 == 0 && !(d->flags & PN_GEMM_FORCE_TILE64);
-  if ((d->flags & PN_GEMM_FORCE_TILE128x64) || big_m)
+  if ((d->flags & PN_GEMM_FORCE_TILE128x64) || big_m ||
+      ((d->flags & PN_GEMM_FORCE_TILE) && gemm_tile128_narrow(d)))
     return colmajor ? launch_tile<128, 64, 64, 32, A_COL>(p, d->batch, s, d->flags)
                     : launch_tile<128, 64, 64, 32, A_ROW>(p, d->batch, s, d->flags);
   if (d->flags & PN_GEMM_FORCE_TILE)
@@ -1070,6 +1079,9 @@ extern "C" int pn_gemm_group_f32(const pn_gemm_desc* d, int count, void* stream)
   int tiles = 0;
   for (int i = 0; i < count; ++i) {
     if (d[i].flags & PN_GEMM_A_COLMAJOR) return PN_BAD_ARG;
+    // the tile body loads 32 columns of every row unconditionally (see gemm_use_skinny), and a
+    // grouped launch has no skinny kernel to fall back to
+    if (d[i].K < 32) return PN_BAD_ARG;
     if (int rc = pn_fill_params(&d[i], &g.p[i])) return rc;
     g.tile_start[i] = tiles;
     g.mt[i] = pn_cdiv(d[i].M, 64);
@@ -1092,6 +1104,10 @@ static int fill_conv_params(const float* in, const float* Wp, const float* bias,
   if ((int64_t)H * W * Cin >= ((int64_t)1 << 29)) return PN_BAD_ARG;
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
   if (Ho <= 0 || Wo <= 0) return PN_BAD_ARG;
+  // a tap outside the image reads the pixel (oy stride, ox stride) instead (load_chunk; zeroed
+  // when the chunk goes to LDS): that pixel lies inside the image only if (Ho - 1) stride <= H - 1,
+  // i.e. 2 pad <= KH - 1, and the same for KW
+  if (KH <= 0 || KW <= 0 || 2 * pad > (KH < KW ? KH : KW) - 1) return PN_BAD_ARG;
   GemmP p{};
   p.A = in; p.W = Wp; p.bias = bias; p.C = out; p.Res = res;
   p.M = Ho * Wo; p.N = Cout; p.K = KH * KW * Cin;

@@ -275,6 +275,10 @@ extern "C" int pn_winograd_f43_output_f32(const float* Mx, const float* bias, fl
 template <int R>
 __global__ __launch_bounds__(256) void k_winograd_weights(const float* __restrict__ w,
                                                           float* __restrict__ U, int Co, int Ci) {
+  // every product and every sum rounded to double: a fused multiply-add keeps the residue of
+  // G's inexact sixths where the terms cancel (1e-15 in place of an exact 0), so U would depend
+  // on which operations the compiler chose to fuse
+#pragma clang fp contract(off)
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (f >= (int64_t)Co * Ci) return;
   double G[R][3];

@@ -506,14 +506,16 @@ def conv2d_nhwc(x, wp, bias, out, B, H, W, Cin, Cout, KH, KW, pad, relu, big_til
 
 
 def conv2d_ex(x, wp, bias, res, out, B, H, W, Cin, Cout, KH, KW, stride, pad, relu=False,
-              relu_after=False, scratch=None):
-    """General channel-last convolution (stride, residual, ReLU before / after it)."""
+              relu_after=False, scratch=None, tile=None, ksplit=0):
+    """General channel-last convolution (stride, residual, ReLU before / after it).  tile: None
+    (64x64), "128x64" or "128"; ksplit: PN_GEMM_KSPLIT(n) (0: the library's own choice)."""
     Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
     flops = 2.0 * B * Ho * Wo * Cout * KH * KW * Cin
     nbytes = 4.0 * (B * (H * W * Cin + Ho * Wo * Cout * (2 if res is not None else 1))
                     + Cout * KH * KW * Cin)
     flags = (GEMM_RELU if relu else 0) | (GEMM_RELU_AFTER_RES if relu_after else 0) | \
-        _reserve_flag()
+        {None: 0, "128": GEMM_FORCE_TILE, "128x64": GEMM_FORCE_TILE128x64}[tile] | \
+        ((ksplit & 31) << 26) | _reserve_flag()
     _check(_launch("k_gemm_tile<64,64,32,32,A_CONV>", flops, nbytes,
                    lambda: lib().pn_conv2d_nhwc_ex_f32(
                        _ptr(x), _ptr(wp), _ptr(bias), _ptr(res), _ptr(out), B, H, W, Cin, Cout,
