@@ -118,3 +118,12 @@ __device__ __forceinline__ float tap_blend(const Tap& ty, const Tap& tx, float v
                                            float v10, float v11) {
   return ty.l0 * (tx.l0 * v00 + tx.l1 * v01) + ty.l1 * (tx.l0 * v10 + tx.l1 * v11);
 }
+// The same blend with the fused product of each sum spelled out.  In tap_blend that choice is the
+// compiler's contraction: k_bilinear_planar fused l1x v01, k_bilinear_planar4 l0x v00, and the two
+// differed in the last bit.  The plane resamplers (resize.hip, postproc.hip), whose outputs are
+// compared bit for bit with each other, use this form -- the one k_bilinear_planar4 had.
+__device__ __forceinline__ float tap_blend_fused(const Tap& ty, const Tap& tx, float v00,
+                                                 float v01, float v10, float v11) {
+  const float top = fmaf(tx.l0, v00, tx.l1 * v01), bot = fmaf(tx.l0, v10, tx.l1 * v11);
+  return fmaf(ty.l0, top, ty.l1 * bot);
+}

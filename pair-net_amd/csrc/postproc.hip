@@ -4,6 +4,8 @@
 
 // One wave per row.  prob = exp(x - max) / sum over all C logits; the label is the
 // argmax of prob over the first C-1 columns (first index on ties), score its prob.
+// A row whose softmax is NaN (all -inf, a +inf, or a NaN entry) scores NaN; its label is the
+// first NaN among the first C-1 logits (torch's argmax of them), 0 where there is none.
 __global__ __launch_bounds__(256) void k_cls_argmax(const float* __restrict__ logits,
                                                     int64_t* __restrict__ label,
                                                     float* __restrict__ score, int64_t rows,
@@ -14,10 +16,12 @@ __global__ __launch_bounds__(256) void k_cls_argmax(const float* __restrict__ lo
   const float* x = logits + row * C;
   float v[4];
   float mx = -INFINITY;
+  int ni = 0x7fffffff;   // first NaN logit of this lane among the admitted columns
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int c = lane + 64 * j;
     v[j] = (c < C) ? x[c] : -INFINITY;
+    if (c < C - 1 && v[j] != v[j] && c < ni) ni = c;
     mx = fmaxf(mx, v[j]);
   }
   mx = wave_max(mx);
@@ -43,6 +47,12 @@ __global__ __launch_bounds__(256) void k_cls_argmax(const float* __restrict__ lo
     const float ob = __shfl_xor(best, o, 64);
     const int oi = __shfl_xor(bi, o, 64);
     if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+  }
+  if (sum != sum) {      // (wave-uniform) no probability compares: the stated rule above
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ni = min(ni, __shfl_xor(ni, o, 64));
+    bi = ni == 0x7fffffff ? 0 : ni;
+    best = sum;
   }
   if (lane == 0) { label[row] = bi + label_offset; score[row] = best; }
 }
@@ -140,7 +150,9 @@ extern "C" int pn_softmax_fg_f32(const float* logits, float* probs, float* fg, i
 }
 
 // First-index argmax of each row (torch.max(-1)[1] on the matching scores,
-// baseline.py:398-399).  One wave per row.
+// baseline.py:398-399).  One wave per row.  An all -inf row gives 0.  A NaN in a column >= 64
+// is skipped (torch would return its position); one in columns 0..63 is taken as its lane's
+// value, never replaced, and hides what would have merged into that lane (in column 0: answer 0).
 __global__ __launch_bounds__(256) void k_row_argmax(const float* __restrict__ x,
                                                     int64_t* __restrict__ idx, int64_t rows,
                                                     int n) {
@@ -302,21 +314,12 @@ __device__ __forceinline__ void resize_kept_pixel(const float* __restrict__ in,
                                                   int64_t e, int oy, int ox, int hi, int wi,
                                                   int ho, int wo) {
   const int64_t per_plane = (int64_t)ho * wo;
-  // same index / lambda arithmetic as k_bilinear_planar (resize.hip)
-  const float sy = (float)hi / (float)ho, sx = (float)wi / (float)wo;
-  float fy = sy * ((float)oy + 0.5f) - 0.5f, fx = sx * ((float)ox + 0.5f) - 0.5f;
-  if (fy < 0.f) fy = 0.f;
-  if (fx < 0.f) fx = 0.f;
-  int y0 = (int)fy, x0 = (int)fx;
-  if (y0 > hi - 1) y0 = hi - 1;
-  if (x0 > wi - 1) x0 = wi - 1;
-  const int y1 = y0 + (y0 < hi - 1 ? 1 : 0), x1 = x0 + (x0 < wi - 1 ? 1 : 0);
-  const float ly1 = fy - (float)y0, lx1 = fx - (float)x0;
-  const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
+  // the taps and the blend of the plane resamplers (common.h): the bits of k_bilinear_planar
+  const Tap ty = make_tap(oy, hi, ho), tx = make_tap(ox, wi, wo);
   const float* ib = in + (int64_t)st->kept[j] * hi * wi;
-  const float v00 = ib[(int64_t)y0 * wi + x0], v01 = ib[(int64_t)y0 * wi + x1];
-  const float v10 = ib[(int64_t)y1 * wi + x0], v11 = ib[(int64_t)y1 * wi + x1];
-  out[(int64_t)j * per_plane + e] = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
+  const float v00 = ib[(int64_t)ty.i0 * wi + tx.i0], v01 = ib[(int64_t)ty.i0 * wi + tx.i1];
+  const float v10 = ib[(int64_t)ty.i1 * wi + tx.i0], v11 = ib[(int64_t)ty.i1 * wi + tx.i1];
+  out[(int64_t)j * per_plane + e] = tap_blend_fused(ty, tx, v00, v01, v10, v11);
 }
 
 // form 0 (rounds 1-11): one workgroup per 256 pixels of every one of the Q planes; all but

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void k_bilinear_planar(const float* __restrict
   const float* ib = in + pl * hi * wi;
   const float v00 = ib[(int64_t)ty.i0 * wi + tx.i0], v01 = ib[(int64_t)ty.i0 * wi + tx.i1];
   const float v10 = ib[(int64_t)ty.i1 * wi + tx.i0], v11 = ib[(int64_t)ty.i1 * wi + tx.i1];
-  const float r = tap_blend(ty, tx, v00, v01, v10, v11);
+  const float r = tap_blend_fused(ty, tx, v00, v01, v10, v11);
   if (GT0) ((uint8_t*)outv)[pl * per_plane + e] = r > 0.f ? 1 : 0;
   else     ((float*)outv)[pl * per_plane + e] = r;
 }
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void k_bilinear_planar4(const float* __restric
   for (int j = 0; j < 4; ++j) {
     const Tap tx = make_tap(ox + j, wi, wo);
     const float v00 = r0[tx.i0], v01 = r0[tx.i1], v10 = r1[tx.i0], v11 = r1[tx.i1];
-    r[j] = tap_blend(ty, tx, v00, v01, v10, v11);
+    r[j] = tap_blend_fused(ty, tx, v00, v01, v10, v11);
   }
   const int64_t o = pl * ((int64_t)ho * wo) + (int64_t)oy * wo + ox;
   if (GT0) {
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void k_pair_masks(const float* __restrict__ mp
       for (int j = 0; j < COLS; ++j) {
         const float v00 = r0[tx[j].i0], v01 = r0[tx[j].i1];
         const float v10 = r1[tx[j].i0], v11 = r1[tx[j].i1];
-        const float r = tap_blend(ty, tx[j], v00, v01, v10, v11);
+        const float r = tap_blend_fused(ty, tx[j], v00, v01, v10, v11);
         m[j >> 2] |= (r > 0.f ? 1u : 0u) << (8 * (j & 3));
       }
       uint8_t* o = masks + (int64_t)oy * wo + ox;

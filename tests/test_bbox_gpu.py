@@ -127,7 +127,7 @@ def test_query_score_topk_strided_zero_rows_sigmoid(hip):
     valid = (torch.rand(50, generator=g) > 0.3).to(torch.uint8)
     out = torch.empty(2, 50, 256, device=DEV)
     hip.zero_rows(x.to(DEV), valid.to(DEV), out, 2, 50, 256)
-    assert torch.equal(out.cpu(), x * valid.view(1, 50, 1))
+    assert torch.equal(out.cpu(), torch.where(valid.view(1, 50, 1).bool(), x, torch.zeros_like(x)))
     y = torch.tensor([0.3, -4.0, float("inf"), 20.0, -float("inf")])
     o = torch.empty(5, device=DEV)
     hip.sigmoid(y.to(DEV), o)
