@@ -978,6 +978,26 @@ int pn_mha_bwd_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, con
                    int64_t lddk, float* dv, int64_t lddv, const uint32_t* bits,
                    const int32_t* rowall, float* scratch, int B, int Nq, int Nk, float scale,
                    void* stream);
+/* The same backward WITHOUT a mask, the keys split into chunks of pn_mha_keysplit_chunk() across
+ * workgroups (csrc/attn_grad.hip): the relation decoder's cross-attentions of the sibling head
+ * over a memory level (baseline.py:372-386; Nq = 100, Nk up to 16 700, no attention mask).  The
+ * probabilities and dS stay on chip; the softmax's row maximum and sum and the row term
+ * sum_j P dP are recomputed per chunk and combined in ascending chunk order.  The logits' dots,
+ * dP = dout . v, the row term and the difference dP - row term are formed in float64 (the row term
+ * is NOT taken as dout . out from a saved output): under a peaked softmax an fp32 difference
+ * leaves whole dk rows with a relative error of 1e-5.  dq / dk / dv are accumulated in fp32; no
+ * atomics, two launches give equal bits, every element of dq / dk / dv is written.  All seven row
+ * strides are free (>= 256, multiples of 4; bases 16-byte aligned); any Nq, Nk >= 1, B <= 65535.
+ * scratch: pn_mha_bwd_keysplit_scratch_floats(B, Nq, Nk) = B * 8 * Nq * (6 + 32 * chunks) floats
+ * (the row statistics and the per-chunk dq partials); a smaller `scratch_floats` is refused before
+ * any launch. */
+int pn_mha_keysplit_chunk(void);
+int64_t pn_mha_bwd_keysplit_scratch_floats(int B, int Nq, int Nk);
+int pn_mha_bwd_keysplit_f32(const float* q, int64_t ldq, const float* k, int64_t ldk,
+                            const float* v, int64_t ldv, const float* dout, int64_t ldo,
+                            float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv,
+                            int64_t lddv, float* scratch, int64_t scratch_floats, int B, int Nq,
+                            int Nk, float scale, void* stream);
 /* Backward of pn_gather_rows_f32: out[b][row][0:length] (+)= sum_{s: index[b][s] == row}
  * src[b][s][0:length]; src [B*slots][ld_src], out [B*rows_out][ld_out]. */
 int pn_scatter_rows_add_f32(const float* src, int64_t ld_src, const int64_t* index, float* out,

@@ -23,7 +23,11 @@ from .head import CrossHead2
 
 
 class CrossHeadBaseline(CrossHead2):
-    """Drop-in for the reference's `CrossHeadBaseline` (inference half)."""
+    """Drop-in for the reference's `CrossHeadBaseline`: the inference half, the loss dict
+    (`seg_losses`, `full_losses`) and the backward behind its logit gradients -- `seg_backward` /
+    `segmenter_backward` for the segmentation terms alone, `head_backward` / `full_backward` for all
+    six gradients, relation branch included (seg_grad.py).  Not carried further: a trainer or
+    optimizer step, `reduce_mean` across ranks, the backbone below the feature gradients."""
 
     _pair_masks_fusable = False      # (CrossHead2.fused_pair_masks: not for this head)
 
@@ -46,6 +50,7 @@ class CrossHeadBaseline(CrossHead2):
         self._rel_loss = None
         self._seg_tape = None
         self._segpd_tape = None
+        self._head_tape = None
         super().__init__(num_classes, in_channels, num_relations, num_obj_query=num_obj_query,
                          num_rel_query=num_rel_query, use_mask=use_mask, **kwargs)
 
@@ -249,6 +254,46 @@ class CrossHeadBaseline(CrossHead2):
         dfeats, g_pd = self._segpd_tape.backward(dmem, dMF, need_dc2=need_dc2)
         assert not set(g_trunk) & set(g_pd)
         out = dict(g_trunk)
+        out.update(g_pd)
+        return dfeats, out
+
+    # ------------------------------------------------------- the whole head's backward
+    def head_backward(self, grads, pl=None, dropout=None):
+        """All six `grads` of `full_losses` carried back through the whole head -- the relation
+        branch (`rel_cls_embed`, the cosine scores, the two update MLPs, the six relation decoder
+        layers) and, with its share added, the class / mask heads and the nine masked layers
+        (`BaselineHeadGrad`, seg_grad.py) -> (dmem [B, SN, 256], dMF [B, H2 * W2, 256], {reference
+        parameter name: gradient}): every head parameter the reference's `losses.backward()`
+        reaches.  Needs the plan of a `return_all_layers=True` forward (default: the last one).
+        `dropout` (an `FfnDropout`): the relation decoder's training-mode FFN dropout in the taped
+        forward; the loss must then have seen the tape's outputs (`BaselineHeadGrad`), so build
+        the tape yourself for that.  `seg_backward` keeps its meaning: the segmentation terms
+        only."""
+        pl = pl if pl is not None else getattr(self, "_last_plan", None)
+        if pl is None or not getattr(pl, "all_layers", False):
+            raise RuntimeError("head_backward needs a forward with return_all_layers=True")
+        if self._seg_loss is None or self._seg_loss.last is None:
+            raise RuntimeError("head_backward needs the grads of a full_losses call")
+        if self._head_tape is None:
+            from .seg_grad import BaselineHeadGrad
+            self._head_tape = BaselineHeadGrad(self)
+        self._head_tape.forward_from_plan(pl, dropout=dropout)
+        return self._head_tape.backward(grads, counts=self._seg_loss.last["counts"])
+
+    def full_backward(self, grads, feats, pl=None, need_dc2=False):
+        """`head_backward(grads, pl)`, then its (dmem, dMF) on through the pixel decoder, FPN branch
+        included, as `segmenter_backward` chains its two parts -> (dfeats, {reference parameter
+        name: gradient}) with dfeats = [d C5, d C4, d C3, d C2 or None without `need_dc2`] (what
+        `BackboneGrad` takes).  The same known limitation as `segmenter_backward`: the pixel
+        decoder's tape runs its own exact-fp32 forward."""
+        dmem, dMF, g_head = self.head_backward(grads, pl)
+        if self._segpd_tape is None:
+            from .seg_grad import SegPixelDecoderGrad
+            self._segpd_tape = SegPixelDecoderGrad(self)
+        self._segpd_tape.forward(feats)
+        dfeats, g_pd = self._segpd_tape.backward(dmem, dMF, need_dc2=need_dc2)
+        assert not set(g_head) & set(g_pd)
+        out = dict(g_head)
         out.update(g_pd)
         return dfeats, out
 

@@ -376,6 +376,116 @@ class RelationTailGrad:
         self._acc(dxp, dy1)                                   # identity shortcut
         return dxp, dK, dV
 
+    def _layer_fwd_self_first(self, pre, x, qpos, K, V, B, nq, nk, ffn, scr, drop=None):
+        """`_layer_fwd` in the sibling head's operation order (baseline.py:363-386: self-attention,
+        norm, cross-attention, norm, FFN, norm), unmasked.  mmcv numbers by position: attentions.0
+        is the SELF-attention and norms.0 follows it, attentions.1 is the cross-attention.  The
+        tape keeps the same keys as `_layer_fwd` (y1 / x1: behind the first attention, here the
+        self-attention; y2 / x2: behind the second)."""
+        w, E = self.head.w, self._E
+        M = B * nq
+        as_, ac = pre + "attentions.0.attn.", pre + "attentions.1.attn."
+        Ws, bs = w[as_ + "in_proj_weight"], w[as_ + "in_proj_bias"]
+        Wc, bc = w[ac + "in_proj_weight"], w[ac + "in_proj_bias"]
+        s = dict(x_in=x, K=K, V=V, drop=drop)
+        # self-attention
+        s["xp"] = E(M, 256)
+        hip.add_periodic(x, qpos, s["xp"])
+        s["QKVs"] = E(M, 768)                               # columns [Q | K | V]
+        hip.linear(s["xp"], Ws[:512], bs[:512], s["QKVs"][:, :512])
+        hip.linear(x, Ws[512:], bs[512:], s["QKVs"][:, 512:])
+        s["att_s"] = E(M, 256)
+        hip.attention(s["QKVs"], 768, s["QKVs"][:, 256:], 768, s["QKVs"][:, 512:], 768, None,
+                      None, s["att_s"], 256, scr, B, nq, nq, self.scale)
+        s["y1"] = E(M, 256)
+        hip.linear(s["att_s"], w[as_ + "out_proj.weight"], w[as_ + "out_proj.bias"], s["y1"], res=x)
+        s["x1"] = E(M, 256)
+        hip.layernorm(s["y1"], w[pre + "norms.0.weight"], w[pre + "norms.0.bias"], s["x1"])
+        # cross-attention
+        s["x1p"] = E(M, 256)
+        hip.add_periodic(s["x1"], qpos, s["x1p"])
+        s["Qc"] = E(M, 256)
+        hip.linear(s["x1p"], Wc[:256], bc[:256], s["Qc"])
+        s["att_c"] = E(M, 256)
+        hip.attention(s["Qc"], 256, K, K.stride(0), V, V.stride(0), None, None, s["att_c"], 256,
+                      scr, B, nq, nk, self.scale)
+        s["y2"] = E(M, 256)
+        hip.linear(s["att_c"], w[ac + "out_proj.weight"], w[ac + "out_proj.bias"], s["y2"],
+                   res=s["x1"])
+        s["x2"] = E(M, 256)
+        hip.layernorm(s["y2"], w[pre + "norms.1.weight"], w[pre + "norms.1.bias"], s["x2"])
+        # FFN
+        s["h"] = E(M, ffn)
+        hip.linear(s["x2"], w[pre + "ffns.0.layers.0.0.weight"],
+                   w[pre + "ffns.0.layers.0.0.bias"], s["h"], relu=True)
+        s["y3"] = E(M, 256)
+        if drop is None:
+            hip.linear(s["h"], w[pre + "ffns.0.layers.1.weight"], w[pre + "ffns.0.layers.1.bias"],
+                       s["y3"], res=s["x2"])
+        else:
+            drop.apply(s["h"], s["h"], 0)
+            hip.linear(s["h"], w[pre + "ffns.0.layers.1.weight"], w[pre + "ffns.0.layers.1.bias"],
+                       s["y3"])
+            drop.apply(s["y3"], s["y3"], 1, res=s["x2"])
+        out = E(M, 256)
+        hip.layernorm(s["y3"], w[pre + "norms.2.weight"], w[pre + "norms.2.bias"], out)
+        return s, out
+
+    def _layer_bwd_self_first(self, pre, s, dx, grads, B, nq, nk, scr, dqpos_rows, dK, dV,
+                              keysplit=False, ks_scr=None):
+        """Backward of `_layer_fwd_self_first`; d K / d V are written into the given 2-D views
+        [B * nk, 256] (free row strides).  `keysplit`: the cross-attention goes through
+        `pn_mha_bwd_keysplit_f32` (scratch `ks_scr`) instead of `pn_mha_bwd_f32` (scratch `scr`);
+        the self-attention always takes the latter.  Returns d input."""
+        w, E = self.head.w, self._E
+        M = B * nq
+        as_, ac = pre + "attentions.0.attn.", pre + "attentions.1.attn."
+        Ws, Wc = w[as_ + "in_proj_weight"], w[ac + "in_proj_weight"]
+        # norm2 <- FFN (as `_layer_bwd`)
+        dy3 = self._ln_bwd(dx, s["y3"], pre + "norms.2.", grads)
+        drop = s["drop"]
+        dz = dy3
+        if drop is not None:
+            dz = E(M, 256)
+            drop.apply(dy3, dz, 1)
+        dh = self._lin_bwd(dz, s["h"], w[pre + "ffns.0.layers.1.weight"], grads,
+                           pre + "ffns.0.layers.1.weight", pre + "ffns.0.layers.1.bias")
+        if drop is not None:
+            drop.apply(dh, dh, 0)
+        hip.relu_bwd(dh, s["h"], dh)
+        dx2 = self._lin_bwd(dh, s["x2"], w[pre + "ffns.0.layers.0.0.weight"], grads,
+                            pre + "ffns.0.layers.0.0.weight", pre + "ffns.0.layers.0.0.bias")
+        self._acc(dx2, dy3)                                   # the FFN's identity shortcut
+        # norm1 <- cross-attention
+        dy2 = self._ln_bwd(dx2, s["y2"], pre + "norms.1.", grads)
+        datt = self._lin_bwd(dy2, s["att_c"], w[ac + "out_proj.weight"], grads,
+                             ac + "out_proj.weight", ac + "out_proj.bias")
+        dQc = E(M, 256)
+        if keysplit:
+            hip.mha_bwd_keysplit(s["Qc"], s["K"], s["V"], datt, dQc, dK, dV, ks_scr, B, nq, nk,
+                                 self.scale)
+        else:
+            hip.mha_bwd(s["Qc"], s["K"], s["V"], datt, dQc, dK, dV, scr, B, nq, nk, self.scale)
+        dx1p = self._lin_bwd(dQc, s["x1p"], Wc[:256], grads, ac + "in_proj_weight",
+                             ac + "in_proj_bias", row0=0)
+        self._acc(dqpos_rows, dx1p)
+        self._acc(dx1p, dy2)                                  # identity shortcut: d x1
+        # norm0 <- self-attention
+        dy1 = self._ln_bwd(dx1p, s["y1"], pre + "norms.0.", grads)
+        datt = self._lin_bwd(dy1, s["att_s"], w[as_ + "out_proj.weight"], grads,
+                             as_ + "out_proj.weight", as_ + "out_proj.bias")
+        dQKV = E(M, 768)
+        hip.mha_bwd(s["QKVs"], s["QKVs"][:, 256:], s["QKVs"][:, 512:], datt, dQKV,
+                    dQKV[:, 256:], dQKV[:, 512:], scr, B, nq, nq, self.scale)
+        dxp = self._lin_bwd(dQKV[:, :512], s["xp"], Ws[:512], grads, as_ + "in_proj_weight",
+                            as_ + "in_proj_bias", row0=0)
+        dxin = self._lin_bwd(dQKV[:, 512:], s["x_in"], Ws[512:], grads, as_ + "in_proj_weight",
+                             as_ + "in_proj_bias", row0=512)
+        self._acc(dqpos_rows, dxp)
+        self._acc(dxin, dxp)
+        self._acc(dxin, dy1)                                  # identity shortcut
+        return dxin
+
     def _relation_forward(self, pair, B, dropout=None):
         """The six Relation Fusion layers over `pair` [B * 2R, 256] with every intermediate kept."""
         head, w, E = self.head, self.head.w, self._E

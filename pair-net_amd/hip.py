@@ -115,6 +115,9 @@ _SIGS = {
     "pn_layernorm256_bwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp]),
     "pn_mha_bwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                                  _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
+    "pn_mha_keysplit_chunk": (C.c_int, []),
+    "pn_mha_bwd_keysplit_scratch_floats": (_i64, [_i32, _i32, _i32]),
+    "pn_mha_bwd_keysplit_f32": (C.c_int, [_vp, _i64] * 7 + [_vp, _i64, _i32, _i32, _i32, _f32, _vp]),
     "pn_scatter_rows_add_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pn_cosine_bwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "pn_mlearner_last_bwd_data_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
@@ -1454,6 +1457,28 @@ def mha_bwd(q, k, v, dout, dq, dk, dv, scratch, B, Nq, Nk, scale, bits=None, row
                                 _ptr(dq), ld(dq), _ptr(dk), ld(dk), _ptr(dv), ld(dv),
                                 _ptr(bits, torch.int32), _ptr(rowall, torch.int32), _ptr(scratch),
                                 B, Nq, Nk, scale, _stream()), "pn_mha_bwd_f32")
+
+
+MHA_KEYSPLIT_CHUNK = 256   # KS_CHUNK of csrc/attn_grad.hip (pn_mha_keysplit_chunk(): checked on use)
+
+
+def mha_bwd_keysplit_scratch_floats(B, Nq, Nk):
+    """B * 8 * Nq * (6 + 32 * chunks): row statistics and per-chunk dq partials."""
+    return B * 8 * Nq * (6 + 32 * ((Nk + MHA_KEYSPLIT_CHUNK - 1) // MHA_KEYSPLIT_CHUNK))
+
+
+def mha_bwd_keysplit(q, k, v, dout, dq, dk, dv, scratch, B, Nq, Nk, scale):
+    """Unmasked `mha_bwd` with the keys split across workgroups (pn_mha_bwd_keysplit_f32): the
+    same 2-D views (any row stride)."""
+    ld = lambda t: _rowmajor(t)[1]
+    L = lib()
+    if L.pn_mha_keysplit_chunk() != MHA_KEYSPLIT_CHUNK:
+        raise RuntimeError("libpairnet_hip.so: key chunk %d, bindings %d; rebuild"
+                           % (L.pn_mha_keysplit_chunk(), MHA_KEYSPLIT_CHUNK))
+    _check(L.pn_mha_bwd_keysplit_f32(_ptr(q), ld(q), _ptr(k), ld(k), _ptr(v), ld(v), _ptr(dout),
+                                     ld(dout), _ptr(dq), ld(dq), _ptr(dk), ld(dk), _ptr(dv),
+                                     ld(dv), _ptr(scratch), scratch.numel(),
+                                     B, Nq, Nk, scale, _stream()), "pn_mha_bwd_keysplit_f32")
 
 
 def scatter_rows_add(src, index, out, B, rows_out, slots, length, accumulate=False):

@@ -25,15 +25,21 @@ them, and the heads' evaluation on the initial queries feeds only a mask, so it 
 second share to dmem), then `PixelDecoderGrad`'s walk through the encoder and the input
 convolutions on the sum.
 
-Not carried further here: the backbone below the feature gradients (`BackboneGrad` takes them), the
-relation branch, `reduce_mean` across ranks, an optimizer step.
+`BaselineHeadGrad` adds the sibling head's relation branch to the first tape: the "rel",
+"subject_scores" and "object_scores" gradients of `full_losses` through `rel_cls_embed`, the cosine
+scores, the two update MLPs and the six relation decoder layers (whose cross-attention backward over
+a memory level is csrc/attn_grad.hip's key-split kernel), their shares added into the final queries'
+gradient, dmem and `level_embed`.
+
+Not carried further here: the backbone below the feature gradients (`BackboneGrad` takes them),
+`reduce_mean` across ranks, an optimizer step.
 """
 import torch
 
 from . import hip
 from .grad import HeadGrad, PixelDecoderGrad, RelationTailGrad
 
-__all__ = ["SegmenterHeadGrad", "SegPixelDecoderGrad"]
+__all__ = ["SegmenterHeadGrad", "BaselineHeadGrad", "SegPixelDecoderGrad"]
 
 
 class SegmenterHeadGrad(HeadGrad):
@@ -169,13 +175,16 @@ class SegmenterHeadGrad(HeadGrad):
 
     @torch.no_grad()
     @hip.on_device
-    def backward(self, grads, on_ready=None, counts=None):
+    def backward(self, grads, on_ready=None, counts=None, seed_dq=None, seed_dmem=None):
         """`grads`: "cls" [L, B, Q, C + 1], "mask" [M, H2, W2] and "mask_rows" [M] as the
         segmentation loss fills them; `counts`: the matched rows per image n_b = min(Q, G_b) (the
         loss object's `last["counts"]`; optional for one image).  Nothing is read back from the
         device.  -> (dmem [B, SN, 256], dMF [B, H2 * W2, 256], {reference parameter name: gradient});
         `self.dq_all` [L, B * Q, 256] keeps the gradient that enters each layer's output from its
-        own heads.  The gradients are views of `self.flat_grad`; `on_ready(end)` as `HeadGrad`."""
+        own heads.  The gradients are views of `self.flat_grad`; `on_ready(end)` as `HeadGrad`.
+        `seed_dq` [B * Q, 256] / `seed_dmem` [B, SN, 256] (`BaselineHeadGrad`): a further gradient
+        into the last layer's output / a memory gradient to accumulate onto (in place); with the
+        default None the launches are the ones this class has always made."""
         if self.st is None:
             raise RuntimeError("backward() needs a forward_from_plan() first")
         g_cls, g_mask, rows, counts = self._check_grads(grads, counts)
@@ -218,12 +227,14 @@ class SegmenterHeadGrad(HeadGrad):
         self.dq_all = dq_all.view(L, B * Q, 256)
         ready(self.group_end["heads"])
         # ---- the nine layers, last to first, each layer's own head gradient added in ----
-        dmem = zeros(B, pl.SN, 256)
+        dmem = zeros(B, pl.SN, 256) if seed_dmem is None else seed_dmem
         dqpos_rows = zeros(B * Q, 256)
         scr = E(max([hip.mha_bwd_scratch_floats(B, Q, n) for n in pl.N] +
                     [hip.mha_bwd_scratch_floats(B, Q, Q)]))
         le, dle = w["level_embed.weight"], grads_out["level_embed.weight"]
         dx = self.dq_all[L - 1].clone()
+        if seed_dq is not None:
+            self._acc(dx, seed_dq)
         for i in reversed(range(L)):
             pre = "transformer_decoder.layers.%d." % i
             ac = pre + "attentions.0.attn."
@@ -254,6 +265,248 @@ class SegmenterHeadGrad(HeadGrad):
         ready(self.group_end["query"])
         ready(self.flat_numel)
         return dmem, dMF, grads_out
+
+
+class BaselineHeadGrad(SegmenterHeadGrad):
+    """`SegmenterHeadGrad` plus the relation branch of `CrossHeadBaseline` (baseline.py:363-399): the
+    six relation decoder layers over the three memory levels (self-attention first), the two
+    two-layer update MLPs on the final queries, the three `F.normalize`s, the two cosine score
+    products and `rel_cls_embed` -- every head parameter autograd reaches behind the reference's
+    `losses.backward()`, and the complete dmem / dMF:
+
+        tape = BaselineHeadGrad(head); head.forward(...)      (return_all_layers=True)
+        out = tape.forward_from_plan(head._last_plan)          # + rel, subject_scores, object_scores
+        losses = head.full_losses(..., grads=g)
+        dmem, dMF, grads = tape.backward(g, counts=n_b)
+
+    The walk: `rel_cls_embed`; the score products with the normalisations (`pn_cosine_bwd_f32` on
+    all three sides: R == Q; d r = the class share, then the subject share, then the object share);
+    the update MLPs -> the gradient into the final queries; the relation layers last to first,
+    each layer's d K / d V on to the memory, `level_embed` and the layer's own in_proj rows
+    256-767; `rel_query_feat` / `rel_query_embed`; then the parent's walk with the final queries'
+    share added into layer 8's incoming gradient and the memory / `level_embed` shares summed in.
+    The new parameter groups come first in the flat buffer, in completion order.
+
+    `attn_bwd_algo`: the relation layers' cross-attention backward, "keysplit"
+    (`pn_mha_bwd_keysplit_f32`: keys split across workgroups, P and dS on chip) or "mha_bwd"
+    (`pn_mha_bwd_f32`); the self-attentions always take the latter.  The argmax ids and the four
+    output gathers carry no loss term and are not taped."""
+
+    ATTN_BWD_ALGOS = ("keysplit", "mha_bwd")
+    REL_KEYS = ("rel", "subject_scores", "object_scores")
+
+    def __init__(self, head, flat=None, base=0):
+        if not hasattr(head, "_relation_stage") or head.num_obj_query != head.num_rel_query:
+            raise RuntimeError("BaselineHeadGrad needs a CrossHeadBaseline")
+        super().__init__(head, flat, base)
+        self.rt = None
+        self._zeroed = False
+        # the cross-attentions' backward: "keysplit" (0.61 against 1.67 ms at 16 700 keys, slower at
+        # 1 050: 0.21 against 0.14; labnotes R23.4) or "mha_bwd"
+        self.attn_bwd_algo = "keysplit"
+
+    @staticmethod
+    def param_groups(head):
+        groups = [("rel_cls_embed", ["rel_cls_embed.weight", "rel_cls_embed.bias"])]
+        for side in ("sub", "obj"):
+            groups.append((side + "_query_update", ["%s_query_update.%d.%s" % (side, j, n)
+                                                    for j in (2, 0) for n in ("weight", "bias")]))
+        for i in reversed(range(head.num_rel_layers)):
+            groups.append(("relation_decoder.layers.%d" % i,
+                           RelationTailGrad._layer_names("relation_decoder.layers.%d." % i)))
+        groups.append(("rel_query", ["rel_query_feat.weight", "rel_query_embed.weight"]))
+        return groups + SegmenterHeadGrad.param_groups(head)
+
+    def _zero_grads(self):
+        if not self._zeroed:            # (the parent's walk runs inside backward(): zeroed once)
+            self.flat_grad.zero_()
+        return self.grads
+
+    # ------------------------------------------------------------------ forward with a tape
+    @torch.no_grad()
+    @hip.on_device
+    def forward_from_plan(self, pl, with_mask=False, dropout=None):
+        """The parent's replay, then the relation stage of `CrossHeadBaseline._relation_stage` taped
+        on the exact-fp32 kernels over the plan's `rKp` / `rVp`.  Returns the parent's dict plus
+        "rel" [B, R, C + 1], "subject_scores" and "object_scores" [B, R, Q].
+
+        `dropout` (an `FfnDropout`, as `TailTrainer` passes it; default None: the deterministic
+        step): the relation decoder's training-mode `ffn_drop`, through the same two `drop.apply`
+        sites per layer as `RelationTailGrad`.  With dropout the plan's own relation outputs are the
+        eval-mode ones: the TAPED outputs returned here are what the loss must see."""
+        self.rt = None
+        out = SegmenterHeadGrad.forward_from_plan(self, pl, with_mask)
+        head, w, E = self.head, self.head.w, self._E
+        B, Q, R = pl.B, self.Q, self.R
+        nr = head.num_rel_layers
+        if not hasattr(pl, "rKp") or len(pl.rKp) != nr:
+            raise RuntimeError("the plan has no relation stage (a CrossHeadBaseline forward)")
+        x = E(B * R, 256)
+        x.view(B, R, 256).copy_(w["rel_query_feat.weight"].unsqueeze(0).expand(B, R, 256))
+        rpos = w["rel_query_embed.weight"]
+        scr = E(max(hip.attn_scratch_floats(B, R, n) for n in list(pl.N) + [R]))
+        layers = []
+        for i in range(nr):
+            l = i % 3
+            s, x = self._layer_fwd_self_first(
+                "relation_decoder.layers.%d." % i, x, rpos, pl.rKp[i].view(B * pl.N[l], 256),
+                pl.rVp[i].view(B * pl.N[l], 256), B, R, pl.N[l], head.rel_ffn, scr,
+                drop=self._drop_of(dropout, i))
+            s["level"] = l
+            layers.append(s)
+        # query matching (baseline.py:388-399) on the last decoder output BEFORE post_norm
+        q = self.dt["q_out"]
+        rt = dict(layers=layers, r_out=x, q=q)
+        for side in ("sub", "obj"):
+            mlp = side + "_query_update"
+            h1, e, hat = E(B * Q, 256), E(B * Q, 256), E(B * Q, 256)
+            hip.linear(q, w[mlp + ".0.weight"], w[mlp + ".0.bias"], h1, relu=True)
+            hip.linear(h1, w[mlp + ".2.weight"], w[mlp + ".2.bias"], e)
+            hip.l2normalize(e, hat)
+            rt[side] = (h1, e, hat)
+        rn = E(B * R, 256)
+        hip.l2normalize(x, rn)
+        rt["rn"] = rn
+        for side, key in (("sub", "subject_scores"), ("obj", "object_scores")):
+            sc = E(B, R, Q)
+            hip.gemm(rn, rt[side][2], sc, M=R, N=Q, K=256, lda=256, ldw=256, ldc=Q, batch=B,
+                     sA=R * 256, sW=Q * 256, sC=R * Q)
+            out[key] = sc
+        C = w["rel_cls_embed.weight"].shape[0]
+        rel = E(B, R, C)
+        hip.linear(x, w["rel_cls_embed.weight"], w["rel_cls_embed.bias"], rel.view(B * R, C))
+        out["rel"] = rel
+        self.rt = rt
+        return out
+
+    # ------------------------------------------------------------------ backward
+    def _check_rel_grads(self, grads):
+        if self.attn_bwd_algo not in self.ATTN_BWD_ALGOS:
+            raise ValueError("attn_bwd_algo %r: one of %s" % (self.attn_bwd_algo,
+                                                               self.ATTN_BWD_ALGOS,))
+        if not isinstance(grads, dict):
+            raise ValueError("grads: the dict `full_losses(..., grads={})` fills")
+        unknown = sorted(set(grads) - set(("cls", "mask", "mask_rows") + self.REL_KEYS))
+        if unknown:
+            raise ValueError("grads has unknown keys %s" % unknown)
+        B, Q, R = self.st["B"], self.Q, self.R
+        C = self.head.w["rel_cls_embed.weight"].shape[0]
+        got = []
+        for k, shape in zip(self.REL_KEYS, ((B, R, C), (B, R, Q), (B, R, Q))):
+            if k not in grads:
+                raise ValueError("grads lacks %r (CrossHeadBaseline.full_losses(..., grads={}))" % k)
+            t = grads[k]
+            if not (torch.is_tensor(t) and t.is_cuda and t.device == self.dev and
+                    t.dtype == torch.float32):
+                raise ValueError("grads[%r]: an fp32 tensor on %s" % (k, self.dev))
+            if tuple(t.shape) != shape:
+                raise ValueError("grads[%r] %s does not match the tape's %s"
+                                 % (k, tuple(t.shape), shape))
+            got.append(t.contiguous())
+        return got
+
+    def _lin_bwd_pad4(self, dy, x, W, grads, wname, bname):
+        """`_lin_bwd` for an output width that is no multiple of 4 (the GEMMs contract over
+        multiples of 4): zero columns / rows, as the parent does for `cls_embed`."""
+        M, n = dy.shape
+        npad = (n + 3) // 4 * 4
+        zeros = lambda *s_: torch.zeros(*s_, device=self.dev, dtype=torch.float32)
+        dyp, Wp = zeros(M, npad), zeros(npad, W.shape[1])
+        dyp[:, :n].copy_(dy)
+        Wp[:n].copy_(W)
+        gp = {"W": zeros(npad, W.shape[1]), "b": zeros(npad)}
+        dx = self._lin_bwd(dyp, x, Wp, gp, "W", "b")
+        self._acc(grads[wname], gp["W"][:n])
+        self._acc(grads[bname], gp["b"][:n])
+        return dx
+
+    @torch.no_grad()
+    @hip.on_device
+    def backward(self, grads, on_ready=None, counts=None):
+        """`grads`: the six entries `CrossHeadBaseline.full_losses(..., grads={})` fills -- the
+        parent's "cls", "mask", "mask_rows" and "rel" [B, R, C + 1], "subject_scores",
+        "object_scores" [B, R, Q]; anything else, a wrong shape / dtype / device or a tape without a
+        relation stage is refused on the host before any launch.  -> (dmem, dMF, {name: gradient})
+        as the parent, now complete; `self.dq_rel` [B * Q, 256] keeps the relation branch's
+        gradient into the final queries."""
+        if self.st is None or self.rt is None:
+            raise RuntimeError("backward() needs a forward_from_plan() with a relation stage first")
+        g_rel, g_sub, g_obj = self._check_rel_grads(grads)
+        self._check_grads(grads, counts)
+        head, w, E, rt = self.head, self.head.w, self._E, self.rt
+        pl = self.dt["pl"]
+        B, Q, R = pl.B, self.Q, self.R
+        ready = on_ready if on_ready is not None else (lambda end: None)
+        zeros = lambda *s_: torch.zeros(*s_, device=self.dev, dtype=torch.float32)
+        self._zeroed = False
+        g = self._zero_grads()
+        # ---- rel_cls_embed ----
+        C = g_rel.shape[-1]
+        dr = self._lin_bwd_pad4(g_rel.view(B * R, C), rt["r_out"], w["rel_cls_embed.weight"], g,
+                                "rel_cls_embed.weight", "rel_cls_embed.bias")
+        ready(self.group_end["rel_cls_embed"])
+        # ---- the two score products and the three normalisations (each backward is linear:
+        # d r = class share + subject share + object share, in this order) ----
+        dq_rel = zeros(B * Q, 256)
+        for side, gs in (("sub", g_sub), ("obj", g_obj)):
+            h1, e, hat = rt[side]
+            dshare, de = E(B * R, 256), E(B * Q, 256)
+            hip.cosine_bwd(gs, rt["r_out"], hat, dshare, B, Q, False)
+            self._acc(dr, dshare)
+            hip.cosine_bwd(gs, e, rt["rn"], de, B, Q, True)
+            # ---- the side's update MLP (Linear, ReLU, Linear) -> the final queries ----
+            mlp = side + "_query_update"
+            d1 = self._lin_bwd(de, h1, w[mlp + ".2.weight"], g, mlp + ".2.weight", mlp + ".2.bias")
+            hip.relu_bwd(d1, h1, d1)
+            self._acc(dq_rel, self._lin_bwd(d1, rt["q"], w[mlp + ".0.weight"], g,
+                                            mlp + ".0.weight", mlp + ".0.bias"))
+            ready(self.group_end[mlp])
+        self.dq_rel = dq_rel
+        # ---- the six relation layers, last to first ----
+        keysplit = self.attn_bwd_algo == "keysplit"
+        dmem = zeros(B, pl.SN, 256)
+        drpos_rows = zeros(B * R, 256)
+        scr = E(max([hip.mha_bwd_scratch_floats(B, R, R)] +
+                    ([] if keysplit else [hip.mha_bwd_scratch_floats(B, R, n) for n in pl.N])))
+        ks_scr = E(max(hip.mha_bwd_keysplit_scratch_floats(B, R, n) for n in pl.N)) \
+            if keysplit else None
+        le, dle = w["level_embed.weight"], g["level_embed.weight"]
+        dx = dr
+        for i in reversed(range(head.num_rel_layers)):
+            pre = "relation_decoder.layers.%d." % i
+            ac = pre + "attentions.1.attn."
+            Wc = w[ac + "in_proj_weight"]
+            s = rt["layers"][i]
+            l, Nk = s["level"], pl.N[s["level"]]
+            dKV = E(B * Nk, 512)                              # columns [dK | dV]
+            dx = self._layer_bwd_self_first(pre, s, dx, g, B, R, Nk, scr, drpos_rows,
+                                            dKV[:, :256], dKV[:, 256:], keysplit, ks_scr)
+            # K = (mem_l + level_embed_l + pe_l) Wk^T + bk, V = (mem_l + level_embed_l) Wv^T + bv
+            # (baseline.py:372-384), image by image, as the parent does for its own layers
+            for b in range(B):
+                mem = pl.X[b, pl.start[l]:pl.start[l] + Nk]
+                memk, memv = E(Nk, 256), E(Nk, 256)
+                hip.add_periodic(mem, pl.dec_kpos[l], memk)
+                hip.add_periodic(mem, le[l:l + 1], memv)
+                dmk = self._lin_bwd(dKV[b * Nk:(b + 1) * Nk, :256], memk, Wc[256:512], g,
+                                    ac + "in_proj_weight", ac + "in_proj_bias", row0=256)
+                dmv = self._lin_bwd(dKV[b * Nk:(b + 1) * Nk, 256:], memv, Wc[512:], g,
+                                    ac + "in_proj_weight", ac + "in_proj_bias", row0=512)
+                self._acc(dmk, dmv)
+                dm = dmem[b, pl.start[l]:pl.start[l] + Nk]
+                self._acc(dm, dmk)
+                hip.colsum(dmk, dle[l], accumulate=True)
+            ready(self.group_end["relation_decoder.layers.%d" % i])
+        hip.batch_sum(dx, g["rel_query_feat.weight"], B)
+        hip.batch_sum(drpos_rows, g["rel_query_embed.weight"], B)
+        ready(self.group_end["rel_query"])
+        # ---- the parent's walk on top of the three shares ----
+        self._zeroed = True
+        try:
+            return SegmenterHeadGrad.backward(self, grads, on_ready, counts, seed_dq=dq_rel,
+                                              seed_dmem=dmem)
+        finally:
+            self._zeroed = False
 
 
 class SegPixelDecoderGrad(PixelDecoderGrad):
