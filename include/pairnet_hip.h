@@ -998,6 +998,22 @@ int pn_mha_bwd_keysplit_f32(const float* q, int64_t ldq, const float* k, int64_t
                             float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv,
                             int64_t lddv, float* scratch, int64_t scratch_floats, int B, int Nq,
                             int Nk, float scale, void* stream);
+/* pn_mha_bwd_keysplit_f32 UNDER the forward's packed boolean mask: the nine masked decoder layers'
+ * cross-attentions (pairnet_head.py:302-312 / baseline.py:254-296).  bits [B * Nq][(Nk + 31) / 32]
+ * and rowall [B * Nq] exactly as pn_mask_pack writes them: a set bit = the key is not attendable,
+ * shared by the 8 heads; a row with rowall == 1 ignores its bits (as pn_mha_bwd_f32 and the
+ * forward do).  Both NULL: no mask, the launches and bits of pn_mha_bwd_keysplit_f32; one given
+ * without the other is PN_BAD_ARG before any launch.  A masked (query, key) pair has P = 0 and
+ * dS = 0 exactly; a key masked in every row gets zero dk / dv rows, which are still written; a
+ * chunk whose keys are all masked for a row has the weight 0 in the combination (no exponential of
+ * (-inf) - (-inf) is formed).  Same float64 places, same fixed summation orders (no atomics, two
+ * launches give equal bits), same operand rules and the same scratch size as the unmasked entry. */
+int pn_mha_bwd_keysplit_masked_f32(const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                   const float* v, int64_t ldv, const float* dout, int64_t ldo,
+                                   float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv,
+                                   int64_t lddv, float* scratch, int64_t scratch_floats, int B,
+                                   int Nq, int Nk, float scale, const uint32_t* bits,
+                                   const int32_t* rowall, void* stream);
 /* Backward of pn_gather_rows_f32: out[b][row][0:length] (+)= sum_{s: index[b][s] == row}
  * src[b][s][0:length]; src [B*slots][ld_src], out [B*rows_out][ld_out]. */
 int pn_scatter_rows_add_f32(const float* src, int64_t ld_src, const int64_t* index, float* out,

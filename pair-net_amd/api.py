@@ -15,6 +15,7 @@ from .grad import (BackboneGrad, FfnDropout, HeadGrad, PixelDecoderGrad,  # noqa
                    RelationTailGrad, SwinBackboneGrad)
 from .seg_grad import BaselineHeadGrad, SegmenterHeadGrad, SegPixelDecoderGrad  # noqa: F401
 from .train import TailTrainer  # noqa: F401
+from .baseline_train import BaselineTrainer  # noqa: F401
 from .seg_losses import Mask2FormerLoss  # noqa: F401
 from .baseline_losses import BaselineRelationLoss  # noqa: F401
 from .preprocess import TestPipeline  # noqa: F401
@@ -32,6 +33,6 @@ __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "Cros
            "baseline_r50", "PSGTrHead2", "psgtr2_head_cfg", "psgtr2_r50", "ResNet50Hip",
            "SwinTransformerHip", "pairnet_swin", "swin_backbone_cfg", "TestPipeline", "test_pipeline_cfg",
            "CrossHeadBBox", "ChannelMapper", "bbox_head_cfg", "channel_mapper_cfg", "cross_r101_vg",
-           "TripletEvaluator", "SceneGraphMetrics", "StreamingEvaluator", "PanopticQuality", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "SegmenterHeadGrad", "BaselineHeadGrad", "SegPixelDecoderGrad", "TailTrainer", "FfnDropout",
+           "TripletEvaluator", "SceneGraphMetrics", "StreamingEvaluator", "PanopticQuality", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "SegmenterHeadGrad", "BaselineHeadGrad", "SegPixelDecoderGrad", "TailTrainer", "BaselineTrainer", "FfnDropout",
            "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg", "Mask2FormerLoss",
            "BaselineRelationLoss"]

@@ -26,8 +26,9 @@ class CrossHeadBaseline(CrossHead2):
     """Drop-in for the reference's `CrossHeadBaseline`: the inference half, the loss dict
     (`seg_losses`, `full_losses`) and the backward behind its logit gradients -- `seg_backward` /
     `segmenter_backward` for the segmentation terms alone, `head_backward` / `full_backward` for all
-    six gradients, relation branch included (seg_grad.py).  Not carried further: a trainer or
-    optimizer step, `reduce_mean` across ranks, the backbone below the feature gradients."""
+    six gradients, relation branch included (seg_grad.py).  The optimizer step over all of it, the
+    backbone included, is `BaselineTrainer` (baseline_train.py).  Not carried further: `reduce_mean`
+    across ranks."""
 
     _pair_masks_fusable = False      # (CrossHead2.fused_pair_masks: not for this head)
 

@@ -660,6 +660,59 @@ class PSGTr:
         return dict(loss=loss, log_vars={k: float(v) for k, v in list(out.items()) + [("loss", loss)]},
                     num_samples=len(img_metas))
 
+    def full_trainer(self, train_backbone=None, **kw):
+        """`trainer()` for the sibling head: builds and keeps a `pairnet_amd.BaselineTrainer` over
+        every parameter the reference's `losses.backward()` reaches behind a `CrossHeadBaseline`
+        (baseline_train.py).  `train_backbone`: None (default) / True trains a ResNet
+        backbone's stages 2-4 (`step` then takes the image), False leaves the backbone frozen
+        (`step` takes its features); True with a Swin backbone raises.  Other keywords go to
+        `BaselineTrainer` (lr, lr_mult, decay_mult, seed, masked_keysplit_min_keys).  `trainer()`,
+        `train_step()` and `val_losses()` keep refusing this head."""
+        from .backbone import ResNet50Hip
+        from .baseline_train import BaselineTrainer
+        if type(self.bbox_head) is not CrossHeadBaseline:
+            raise NotImplementedError("full_trainer is built for CrossHeadBaseline only (%s: "
+                                      "trainer())" % type(self.bbox_head).__name__)
+        resnet = isinstance(self.backbone, ResNet50Hip)
+        if train_backbone is None:
+            train_backbone = resnet
+        if train_backbone and not resnet:
+            raise NotImplementedError("full_trainer trains a ResNet50Hip backbone; a %s backbone is "
+                                      "out of scope (train_backbone=False keeps it frozen)"
+                                      % type(self.backbone).__name__)
+        self._full_trainer = BaselineTrainer(self.bbox_head,
+                                             backbone=self.backbone if train_backbone else None, **kw)
+        return self._full_trainer
+
+    def full_train_step(self, img, img_metas=None, gt_rels=None, gt_bboxes=None, gt_labels=None,
+                        gt_masks=None, num_total_masks=None):
+        """`train_step` for the sibling head, the same two call forms: `forward_train`'s argument
+        order -> the 30 loss terms + `grad_norm` + `assign_status` (device scalars), or
+        `(data_batch, optimizer)` -> mmdet's dict(loss, log_vars, num_samples) with `loss` the sum
+        of the terms whose name contains "loss".  Runs `full_trainer().step` -- the trainer an
+        earlier `full_trainer(...)` call built if there is one, else the default one."""
+        mmdet_form = isinstance(img, dict)
+        if mmdet_form:
+            data = img
+            unwrap = lambda v: getattr(v, "data", v)        # (mmcv DataContainer)
+            first = lambda v: v[0] if isinstance(v, (list, tuple)) and len(v) == 1 and \
+                isinstance(v[0], (list, tuple)) else v
+            img = unwrap(data["img"])
+            if isinstance(img, (list, tuple)):
+                img = img[0]
+            img_metas = first(unwrap(data["img_metas"]))
+            gt_rels, gt_labels = first(unwrap(data["gt_rels"])), first(unwrap(data["gt_labels"]))
+            gt_masks = first(unwrap(data["gt_masks"]))
+        tr = getattr(self, "_full_trainer", None) or self.full_trainer()
+        gt_masks = self._prepare_gt_masks(img, gt_masks)
+        x = img if tr.backbone is not None else self.extract_feat(img)
+        out = tr.step(x, img_metas, gt_rels, gt_labels, gt_masks, num_total_masks=num_total_masks)
+        if not mmdet_form:
+            return out
+        loss = sum(v for k, v in out.items() if "loss" in k)
+        return dict(loss=loss, log_vars={k: float(v) for k, v in list(out.items()) + [("loss", loss)]},
+                    num_samples=len(img_metas))
+
     @torch.no_grad()
     def detect(self, image, rescale=False):
         """Decoded uint8 (H, W, 3) BGR image (cv2 order, host or device) -> [Result]: the

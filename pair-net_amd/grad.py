@@ -325,9 +325,13 @@ class RelationTailGrad:
         hip.layernorm(s["y3"], w[pre + "norms.2.weight"], w[pre + "norms.2.bias"], out)
         return s, out
 
-    def _layer_bwd(self, pre, s, dx, grads, B, nq, nk, scr, dqpos_rows):
+    def _layer_bwd(self, pre, s, dx, grads, B, nq, nk, scr, dqpos_rows, keysplit=False,
+                   ks_scr=None):
         """Backward of `_layer_fwd`: accumulates the layer's parameter gradients and d (x +
-        query_pos) (all three uses) into `dqpos_rows`; returns (d input, d K, d V)."""
+        query_pos) (all three uses) into `dqpos_rows`; returns (d input, d K, d V).  `keysplit`:
+        the masked cross-attention goes through `pn_mha_bwd_keysplit_masked_f32` (scratch `ks_scr`)
+        under the layer's own bits / rowall instead of `pn_mha_bwd_f32` (scratch `scr`); the
+        self-attention always takes the latter."""
         w, E = self.head.w, self._E
         M = B * nq
         ac, as_ = pre + "attentions.0.attn.", pre + "attentions.1.attn."
@@ -368,8 +372,12 @@ class RelationTailGrad:
         datt = self._lin_bwd(dy1, s["att_c"], w[ac + "out_proj.weight"], grads,
                              ac + "out_proj.weight", ac + "out_proj.bias")
         dQc, dK, dV = E(M, 256), E(B * nk, 256), E(B * nk, 256)
-        hip.mha_bwd(s["Qc"], s["K"], s["V"], datt, dQc, dK, dV, scr, B, nq, nk, self.scale,
-                    bits=s["bits"], rowall=s["rowall"])
+        if keysplit:
+            hip.mha_bwd_keysplit(s["Qc"], s["K"], s["V"], datt, dQc, dK, dV, ks_scr, B, nq, nk,
+                                 self.scale, bits=s["bits"], rowall=s["rowall"])
+        else:
+            hip.mha_bwd(s["Qc"], s["K"], s["V"], datt, dQc, dK, dV, scr, B, nq, nk, self.scale,
+                        bits=s["bits"], rowall=s["rowall"])
         dxp = self._lin_bwd(dQc, s["xp"], Wc[:256], grads, ac + "in_proj_weight",
                             ac + "in_proj_bias", row0=0)
         self._acc(dqpos_rows, dxp)

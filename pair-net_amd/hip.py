@@ -118,6 +118,8 @@ _SIGS = {
     "pn_mha_keysplit_chunk": (C.c_int, []),
     "pn_mha_bwd_keysplit_scratch_floats": (_i64, [_i32, _i32, _i32]),
     "pn_mha_bwd_keysplit_f32": (C.c_int, [_vp, _i64] * 7 + [_vp, _i64, _i32, _i32, _i32, _f32, _vp]),
+    "pn_mha_bwd_keysplit_masked_f32": (C.c_int, [_vp, _i64] * 7 + [_vp, _i64, _i32, _i32, _i32, _f32,
+                                                                  _vp, _vp, _vp]),
     "pn_scatter_rows_add_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pn_cosine_bwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "pn_mlearner_last_bwd_data_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
@@ -1467,14 +1469,23 @@ def mha_bwd_keysplit_scratch_floats(B, Nq, Nk):
     return B * 8 * Nq * (6 + 32 * ((Nk + MHA_KEYSPLIT_CHUNK - 1) // MHA_KEYSPLIT_CHUNK))
 
 
-def mha_bwd_keysplit(q, k, v, dout, dq, dk, dv, scratch, B, Nq, Nk, scale):
-    """Unmasked `mha_bwd` with the keys split across workgroups (pn_mha_bwd_keysplit_f32): the
-    same 2-D views (any row stride)."""
+def mha_bwd_keysplit(q, k, v, dout, dq, dk, dv, scratch, B, Nq, Nk, scale, bits=None, rowall=None):
+    """`mha_bwd` with the keys split across workgroups: the same 2-D views (any row stride).
+    Without `bits` / `rowall` the unmasked entry (pn_mha_bwd_keysplit_f32), as always; with either,
+    pn_mha_bwd_keysplit_masked_f32 under the forward's packed mask (pn_mask_pack's outputs; one
+    without the other is refused by the library)."""
     ld = lambda t: _rowmajor(t)[1]
     L = lib()
     if L.pn_mha_keysplit_chunk() != MHA_KEYSPLIT_CHUNK:
         raise RuntimeError("libpairnet_hip.so: key chunk %d, bindings %d; rebuild"
                            % (L.pn_mha_keysplit_chunk(), MHA_KEYSPLIT_CHUNK))
+    if bits is not None or rowall is not None:
+        _check(L.pn_mha_bwd_keysplit_masked_f32(
+            _ptr(q), ld(q), _ptr(k), ld(k), _ptr(v), ld(v), _ptr(dout), ld(dout), _ptr(dq), ld(dq),
+            _ptr(dk), ld(dk), _ptr(dv), ld(dv), _ptr(scratch), scratch.numel(), B, Nq, Nk, scale,
+            _ptr(bits, torch.int32), _ptr(rowall, torch.int32), _stream()),
+            "pn_mha_bwd_keysplit_masked_f32")
+        return
     _check(L.pn_mha_bwd_keysplit_f32(_ptr(q), ld(q), _ptr(k), ld(k), _ptr(v), ld(v), _ptr(dout),
                                      ld(dout), _ptr(dq), ld(dq), _ptr(dk), ld(dk), _ptr(dv),
                                      ld(dv), _ptr(scratch), scratch.numel(),

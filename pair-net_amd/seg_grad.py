@@ -31,8 +31,8 @@ scores, the two update MLPs and the six relation decoder layers (whose cross-att
 a memory level is csrc/attn_grad.hip's key-split kernel), their shares added into the final queries'
 gradient, dmem and `level_embed`.
 
-Not carried further here: the backbone below the feature gradients (`BackboneGrad` takes them),
-`reduce_mean` across ranks, an optimizer step.
+Not carried further here: the backbone below the feature gradients (`BackboneGrad` takes them) and
+the optimizer step (`BaselineTrainer`, baseline_train.py, runs both), `reduce_mean` across ranks.
 """
 import torch
 
@@ -49,7 +49,12 @@ class SegmenterHeadGrad(HeadGrad):
 
     Works on any head with the shared Mask2Former trunk (`CrossHead2`, `CrossHeadBaseline`).  The
     gradients are views of one flat buffer (`flat_grad`, segments padded to 64 floats, groups in
-    completion order, `on_ready(end)`), as the other tapes keep them."""
+    completion order, `on_ready(end)`), as the other tapes keep them.
+
+    `masked_keysplit_min_keys` (default None): the nine masked cross-attentions' backward.  None is
+    `pn_mha_bwd_f32` for every layer; an integer sends the layers whose memory level has at least
+    that many keys through `pn_mha_bwd_keysplit_masked_f32` (csrc/attn_grad.hip) under the layer's
+    own bits / rowall (faster from 4 200 keys on, slower at 1 050: labnotes R24.4)."""
 
     HEADS_GROUP = ("heads", ["mask_embed.4.weight", "mask_embed.4.bias", "mask_embed.2.weight",
                              "mask_embed.2.bias", "mask_embed.0.weight", "mask_embed.0.bias",
@@ -61,6 +66,10 @@ class SegmenterHeadGrad(HeadGrad):
         super().__init__(head, flat, base)
         self.st = None
         self._tables = {}
+        # the nine masked cross-attentions' backward: None (default) is `pn_mha_bwd_f32` everywhere,
+        # today's launches and bits; an integer sends the layers whose memory level has at least
+        # that many keys through `pn_mha_bwd_keysplit_masked_f32` (0: all nine)
+        self.masked_keysplit_min_keys = None
 
     @staticmethod
     def param_groups(head):
@@ -188,6 +197,9 @@ class SegmenterHeadGrad(HeadGrad):
         if self.st is None:
             raise RuntimeError("backward() needs a forward_from_plan() first")
         g_cls, g_mask, rows, counts = self._check_grads(grads, counts)
+        mk = self.masked_keysplit_min_keys
+        if mk is not None and (isinstance(mk, bool) or not isinstance(mk, int) or mk < 0):
+            raise ValueError("masked_keysplit_min_keys %r: None or an integer >= 0" % (mk,))
         head, w, E, st = self.head, self.head.w, self._E, self.st
         pl, layers = self.dt["pl"], self.dt["layers"]
         B, Q, L = st["B"], self.Q, st["L"]
@@ -229,8 +241,12 @@ class SegmenterHeadGrad(HeadGrad):
         # ---- the nine layers, last to first, each layer's own head gradient added in ----
         dmem = zeros(B, pl.SN, 256) if seed_dmem is None else seed_dmem
         dqpos_rows = zeros(B * Q, 256)
-        scr = E(max([hip.mha_bwd_scratch_floats(B, Q, n) for n in pl.N] +
+        mk = self.masked_keysplit_min_keys
+        ks_levels = [n for n in pl.N if mk is not None and n >= mk]
+        scr = E(max([hip.mha_bwd_scratch_floats(B, Q, n) for n in pl.N if n not in ks_levels] +
                     [hip.mha_bwd_scratch_floats(B, Q, Q)]))
+        ks_scr = E(max(hip.mha_bwd_keysplit_scratch_floats(B, Q, n) for n in ks_levels)) \
+            if ks_levels else None                       # (allocated only when a layer uses it)
         le, dle = w["level_embed.weight"], grads_out["level_embed.weight"]
         dx = self.dq_all[L - 1].clone()
         if seed_dq is not None:
@@ -241,7 +257,11 @@ class SegmenterHeadGrad(HeadGrad):
             Wc = w[ac + "in_proj_weight"]
             s = layers[i]
             l, Nk = s["level"], pl.N[s["level"]]
-            dx, dK, dV = self._layer_bwd(pre, s, dx, grads_out, B, Q, Nk, scr, dqpos_rows)
+            if mk is not None and Nk >= mk:
+                dx, dK, dV = self._layer_bwd(pre, s, dx, grads_out, B, Q, Nk, scr, dqpos_rows,
+                                             True, ks_scr)
+            else:
+                dx, dK, dV = self._layer_bwd(pre, s, dx, grads_out, B, Q, Nk, scr, dqpos_rows)
             if i > 0:                            # deep supervision: layer i - 1's output has heads
                 self._acc(dx, self.dq_all[i - 1])
             # K = (mem_l + level_embed_l + pe_l) Wk^T + bk, V = (mem_l + level_embed_l) Wv^T + bv
