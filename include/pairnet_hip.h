@@ -1093,6 +1093,24 @@ int pn_window_attention_bwd_f32(const float* qkv, int64_t ldqkv, const float* qk
                                 const float* out, int64_t ldo, float* dqkv, int64_t lddqkv,
                                 float* dtable_part, int B, int H, int W, int C, int heads, int ws,
                                 int shift, float scale, void* stream);
+/* Backward of pn_patch_merge_ln_f32 ([3P] mmdet PatchMerging: nn.Unfold(2, stride 2) + LayerNorm(4C),
+ * before its reduction Linear), for a Swin backbone whose lower stages train
+ * (configs/deformable_detr/cross_swinb_vg.py:202-226, frozen_stages=-1; grad.py SwinStagesGrad).
+ * Added at ABI 34 (additive).  dy [B*H2*W2][4C] the gradient of the merged, normalised rows
+ * (H2 = ceil(H/2), W2 = ceil(W/2)), x [B][H*W][C] the saved un-merged map, gamma [4C] in the
+ * forward's neighbour-major order ->
+ *   dx [B][H*W][C]: every row written exactly once (accumulate != 0: added to what is there -- the
+ *     stage output also feeds its output norm).  The gradient of the zero padding beyond an odd
+ *     map's edge is dropped; the padding still counts in the rows' moments and backward sums;
+ *   part [nblocks][2][4C]: per-workgroup sums of dy xhat | dy, neighbour-major; their column sum
+ *     (pn_colsum_f32 over nblocks rows of 8C floats) is d gamma | d beta.
+ * nblocks (the launch's workgroups, 1 .. 65535; any value is correct): pair-net_amd/hip.py
+ * patch_merge_ln_bwd_nblocks gives min(ceil(rows / 4), 512).  The gathered [rows][4C] input is never
+ * formed; no atomics, two launches give equal bits.  Refuses (-1, nothing written) C % 4 != 0,
+ * 4C > 3072, B / H / W < 1, null or mis-aligned (16 B) pointers. */
+int pn_patch_merge_ln_bwd_f32(const float* dy, const float* x, const float* gamma, float* dx,
+                              float* part, int nblocks, int B, int H, int W, int C, float eps,
+                              int accumulate, void* stream);
 /* out[ci][T-1-t][co] = in[co][t][ci]: a "same" convolution's weight as its data gradient reads it */
 int pn_conv_weight_bwd_layout_f32(const float* in, float* out, int Co, int T, int Ci, void* stream);
 /* Training-mode dropout of the Relation Fusion decoder's FFN (csrc/dropout.hip): mmcv FFN.layers'

@@ -12,7 +12,7 @@ from .neck import ChannelMapper  # noqa: F401
 from .head import CrossHead2  # noqa: F401
 from .pipeline import PipelinedHead  # noqa: F401
 from .grad import (BackboneGrad, FfnDropout, HeadGrad, PixelDecoderGrad,  # noqa: F401
-                   RelationTailGrad, SwinBackboneGrad)
+                   RelationTailGrad, SwinBackboneGrad, SwinStagesGrad)
 from .seg_grad import BaselineHeadGrad, SegmenterHeadGrad, SegPixelDecoderGrad  # noqa: F401
 from .train import TailTrainer  # noqa: F401
 from .baseline_train import BaselineTrainer  # noqa: F401
@@ -33,6 +33,6 @@ __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "Cros
            "baseline_r50", "PSGTrHead2", "psgtr2_head_cfg", "psgtr2_r50", "ResNet50Hip",
            "SwinTransformerHip", "pairnet_swin", "swin_backbone_cfg", "TestPipeline", "test_pipeline_cfg",
            "CrossHeadBBox", "ChannelMapper", "bbox_head_cfg", "channel_mapper_cfg", "cross_r101_vg",
-           "TripletEvaluator", "SceneGraphMetrics", "StreamingEvaluator", "PanopticQuality", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "SegmenterHeadGrad", "BaselineHeadGrad", "SegPixelDecoderGrad", "TailTrainer", "BaselineTrainer", "FfnDropout",
+           "TripletEvaluator", "SceneGraphMetrics", "StreamingEvaluator", "PanopticQuality", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "SwinStagesGrad", "SegmenterHeadGrad", "BaselineHeadGrad", "SegPixelDecoderGrad", "TailTrainer", "BaselineTrainer", "FfnDropout",
            "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg", "Mask2FormerLoss",
            "BaselineRelationLoss"]

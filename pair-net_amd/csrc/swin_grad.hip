@@ -8,6 +8,9 @@
 //   k_window_attn_bwd    (shifted-)window attention backward: dq / dk / dv over the padded,
 //                        un-shifted token grid and per-(image, window, head) partials of the
 //                        relative-position-bias-table gradient
+//   k_patch_merge_ln_bwd  backward of the fused 2x2 gather + LayerNorm(4C) of patch merging
+//                        (pn_patch_merge_ln_f32): dx over the un-merged map, per-workgroup
+//                        partials of d gamma / d beta (grad.py SwinStagesGrad: every stage trains)
 // All sums run in a fixed order (no atomics): the gradients are bitwise reproducible.
 #include "common.h"
 
@@ -89,6 +92,152 @@ extern "C" int pn_layernorm_rows_bwd_f32(const float* dy, int64_t lddy, const fl
     return PN_BAD_ARG;
   hipLaunchKernelGGL(k_ln_rows_bwd, dim3(pn_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, dy,
                      lddy, x, ldx, gamma, dx, lddx, gxhat, ldg, rows, C, eps);
+  return PN_LAUNCH_CHECK();
+}
+
+// ---- patch merging: backward of the fused gather + LayerNorm (k_ln_rows<MERGE>, swin.hip) -------
+// Merged row (b, y2, x2) = [x(2y2, 2x2) | x(2y2, 2x2+1) | x(2y2+1, 2x2) | x(2y2+1, 2x2+1)], zeros
+// beyond an odd map's edge; gamma in the same neighbour-major order.  Every token of the H x W
+// map belongs to exactly one merged row, so the adjoint of the gather is a permutation: the wave
+// that owns a merged row writes the (up to) four C-runs of dx it was gathered from, each exactly
+// once, and nothing else does.  The [rows][4C] gathered input is never formed: the row is
+// re-gathered from x into registers and its moments recomputed as the forward computes them.  A
+// padding position's xhat = -mean rstd is NOT zero: it stays in the row's two backward sums and
+// in d gamma / d beta, only its dx has nowhere to go and is dropped.
+// One wave per merged row at a time, NV float4 per lane (4C <= 256 NV); a workgroup's four waves
+// walk rows blockIdx.x * 4 + wave, + 4 gridDim.x, ... and keep their sums of dy xhat and dy in
+// registers.  At the end the waves are added in the order ((0 + 1) + 2) + 3 through LDS and the
+// workgroup writes ONE partial row [2][4C] (dy xhat | dy): pn_colsum_f32 over the [nblocks] rows
+// gives d gamma | d beta in a fixed order.  Row reductions are cross-lane (wave_sum), no LDS.
+struct MergeBP { int H, W, H2, W2, C; };
+
+template <int NV>
+__global__ __launch_bounds__(256) void k_patch_merge_ln_bwd(const float* __restrict__ dy,
+                                                            const float* __restrict__ x,
+                                                            const float* __restrict__ gamma,
+                                                            float* dx, float* __restrict__ part,
+                                                            int64_t rows, MergeBP mp, float eps,
+                                                            int accumulate) {
+  extern __shared__ __attribute__((aligned(16))) float red[];     // [2][4C]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int C4 = 4 * mp.C;
+  const int64_t per = (int64_t)mp.H2 * mp.W2;
+  float4 ag[NV], ab[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) ag[i] = ab[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
+    const int64_t img = row / per;
+    const int r = (int)(row - img * per);
+    const int y2 = r / mp.W2, x2 = r - y2 * mp.W2;
+    // element offset of this lane's i-th float4 in x / dx, -1: padding (or past the row)
+    auto src = [&](int c) -> int64_t {
+      const int q = c / mp.C, cc = c - q * mp.C;
+      const int yy = 2 * y2 + (q >> 1), xx = 2 * x2 + (q & 1);
+      return (yy < mp.H && xx < mp.W) ? ((img * mp.H + yy) * mp.W + xx) * mp.C + cc : -1;
+    };
+    float4 v[NV], d[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = i * 256 + lane * 4;
+      v[i] = d[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c < C4) {
+        const int64_t o = src(c);
+        if (o >= 0) v[i] = ld4(x + o);
+        d[i] = ld4(dy + row * C4 + c);
+      }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    const float mean = wave_sum(s) / (float)C4;
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = i * 256 + lane * 4;
+      if (c < C4) {
+        v[i].x -= mean; v[i].y -= mean; v[i].z -= mean; v[i].w -= mean;
+        ss += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
+      }
+    }
+    const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)C4 + eps);
+    float m1 = 0.f, m2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = i * 256 + lane * 4;
+      if (c < C4) {
+        const float4 g = ld4(gamma + c);
+        v[i] = make_float4(v[i].x * rstd, v[i].y * rstd, v[i].z * rstd, v[i].w * rstd);   // xhat
+        ag[i].x += d[i].x * v[i].x; ag[i].y += d[i].y * v[i].y;
+        ag[i].z += d[i].z * v[i].z; ag[i].w += d[i].w * v[i].w;
+        ab[i] = add4(ab[i], d[i]);
+        d[i] = make_float4(d[i].x * g.x, d[i].y * g.y, d[i].z * g.z, d[i].w * g.w);
+        m1 += (d[i].x + d[i].y) + (d[i].z + d[i].w);
+        m2 += (d[i].x * v[i].x + d[i].y * v[i].y) + (d[i].z * v[i].z + d[i].w * v[i].w);
+      }
+    }
+    m1 = wave_sum(m1) / (float)C4;
+    m2 = wave_sum(m2) / (float)C4;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = i * 256 + lane * 4;
+      const int64_t o = c < C4 ? src(c) : -1;
+      if (o >= 0) {
+        float4 t = make_float4(rstd * (d[i].x - m1 - v[i].x * m2), rstd * (d[i].y - m1 - v[i].y * m2),
+                               rstd * (d[i].z - m1 - v[i].z * m2), rstd * (d[i].w - m1 - v[i].w * m2));
+        if (accumulate) t = add4(ld4(dx + o), t);
+        st4(dx + o, t);
+      }
+    }
+  }
+
+  // the four waves' sums in the order ((0 + 1) + 2) + 3; wave 3 writes the workgroup's partial
+  // (every wave reaches every barrier: the row loop has no early exit)
+  float* out = part + (int64_t)blockIdx.x * 2 * C4;
+  for (int w = 0; w < 4; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = i * 256 + lane * 4;
+        if (c < C4) {
+          float4 a = ag[i], b = ab[i];
+          if (w > 0) {
+            a = add4(ld4(red + c), a);
+            b = add4(ld4(red + C4 + c), b);
+          }
+          st4((w < 3 ? red : out) + c, a);
+          st4((w < 3 ? red : out) + C4 + c, b);
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+extern "C" int pn_patch_merge_ln_bwd_f32(const float* dy, const float* x, const float* gamma,
+                                         float* dx, float* part, int nblocks, int B, int H, int W,
+                                         int C, float eps, int accumulate, void* stream) {
+  if (!dy || !x || !gamma || !dx || !part || B <= 0 || H < 1 || W < 1 || C <= 0 || (C & 3) ||
+      4 * C > 256 * LNB_MAXV || nblocks < 1 || nblocks > 65535)
+    return PN_BAD_ARG;
+  if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)gamma | (uintptr_t)dx | (uintptr_t)part) & 15)
+    return PN_BAD_ARG;
+  const MergeBP mp{H, W, (H + 1) / 2, (W + 1) / 2, C};
+  const int64_t rows = (int64_t)B * mp.H2 * mp.W2;
+  const int nv = (4 * C + 255) >> 8;
+  const size_t lds = (size_t)8 * C * sizeof(float);
+  const dim3 grid(nblocks), block(256);
+  hipStream_t s = (hipStream_t)stream;
+#define PMB_LAUNCH(NV)                                                                          \
+  hipLaunchKernelGGL(k_patch_merge_ln_bwd<NV>, grid, block, lds, s, dy, x, gamma, dx, part, rows, \
+                     mp, eps, accumulate)
+  if (nv <= 2) PMB_LAUNCH(2);
+  else if (nv <= 3) PMB_LAUNCH(3);
+  else if (nv <= 4) PMB_LAUNCH(4);
+  else if (nv <= 6) PMB_LAUNCH(6);
+  else if (nv <= 8) PMB_LAUNCH(8);
+  else PMB_LAUNCH(12);
+#undef PMB_LAUNCH
   return PN_LAUNCH_CHECK();
 }
 

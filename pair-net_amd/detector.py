@@ -597,7 +597,13 @@ class PSGTr:
         config trains.  `train_backbone`: None (default) trains a ResNet backbone's
         stages 2-4 and leaves a Swin backbone frozen; True also trains a Swin backbone's last stage
         and norm as configs/mask2former/pairnet_swinb.py does (`frozen_stages=3`,
-        `SwinBackboneGrad`); False freezes either.  Other keywords go to TailTrainer (lr, lr_mult,
+        `SwinBackboneGrad`), or -- for a config with a lower `frozen_stages` -- every stage from
+        there down, with -1 also the patch mergings and the patch embedding
+        (configs/deformable_detr/cross_swinb_vg.py:202-226, `SwinStagesGrad`); False freezes either.
+        `decay_mult` ({substring: weight-decay multiplier}) defaults to the `backbone` custom key
+        of the config's optimizer block when `build_detector` was given one (`optimizer=` beside
+        `backbone=`: paramwise_cfg.custom_keys["backbone"]["decay_mult"], cross_swinb_vg.py:557-573).
+        Other keywords go to TailTrainer (lr, lr_mult,
         group, drop_path, train_decoder=False / train_pixel_decoder=False for the frozen-detector
         regimes; `dropout=True` trains with the relation decoder's configured FFN dropout,
         `seed=` its masks; `device_targets=True` builds the loss targets on the device -- Hungarian
@@ -617,6 +623,10 @@ class PSGTr:
         kw.setdefault("train_pixel_decoder", True)
         if not (kw["train_decoder"] and kw["train_pixel_decoder"]):
             bb = None
+        opt = getattr(self, "optimizer_cfg", None) or {}
+        keys = (opt.get("paramwise_cfg") or {}).get("custom_keys") or {}
+        if bb is not None and "decay_mult" in (keys.get("backbone") or {}):
+            kw.setdefault("decay_mult", {"backbone.": float(keys["backbone"]["decay_mult"])})
         self._trainer = TailTrainer(self.bbox_head, backbone=bb, **kw)
         return self._trainer
 
@@ -1026,6 +1036,8 @@ def build_detector(cfg, train_cfg=None, test_cfg=None):
     if cfg.pop("type", "PSGTr") != "PSGTr":
         raise NotImplementedError("only type='PSGTr'")
     model_train_cfg = cfg.pop("train_cfg", None)
-    return PSGTr(cfg["backbone"], cfg["bbox_head"],
-                 train_cfg=model_train_cfg if model_train_cfg is not None else train_cfg,
-                 test_cfg=cfg.get("test_cfg", test_cfg), neck=cfg.get("neck"))
+    det = PSGTr(cfg["backbone"], cfg["bbox_head"],
+                train_cfg=model_train_cfg if model_train_cfg is not None else train_cfg,
+                test_cfg=cfg.get("test_cfg", test_cfg), neck=cfg.get("neck"))
+    det.optimizer_cfg = cfg.get("optimizer")      # (optional; read by `trainer()` only)
+    return det

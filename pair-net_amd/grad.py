@@ -33,7 +33,7 @@ import torch
 from . import hip
 
 __all__ = ["RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad",
-           "FfnDropout"]
+           "SwinStagesGrad", "FfnDropout"]
 
 
 class FfnDropout(namedtuple("FfnDropout", "p seed subseq step layer")):
@@ -1268,6 +1268,42 @@ class SwinBackboneGrad(RelationTailGrad):
             hip.scale_rows(out, keep)
         hip.add_periodic(out, x, out)
 
+    def _block_fwd(self, p, x, B, h, wd, C, nh, shift, keep):
+        """One SwinBlock `p` on the token rows x [B*h*wd, C] with a tape: (saved tensors, output
+        rows).  `keep` [2, B]: the block's DropPath factors (attention, FFN branch) or None."""
+        w, E, ws = self.head.w, self._E, self.ws
+        n, F = B * h * wd, int(self.head.mlp_ratio * C)
+        s = dict(x=x, shift=shift)
+        s["xn1"] = E(n, C)
+        hip.layernorm_rows(x, w[p + "norm1.weight"], w[p + "norm1.bias"], s["xn1"], self.EPS)
+        s["qkv"] = E(n, 3 * C)
+        hip.linear(s["xn1"], w[p + "attn.w_msa.qkv.weight"], w[p + "attn.w_msa.qkv.bias"], s["qkv"])
+        s["ao"] = E(n, C)
+        hip.window_attention(s["qkv"], w[p + "attn.w_msa.qkv.bias"],
+                             w[p + "attn.w_msa.relative_position_bias_table"], s["ao"], B, h, wd,
+                             C, nh, ws, s["shift"])
+        s["x1"] = E(n, C)
+        if keep is None:
+            hip.linear(s["ao"], w[p + "attn.w_msa.proj.weight"], w[p + "attn.w_msa.proj.bias"],
+                       s["x1"], res=x)
+        else:
+            hip.linear(s["ao"], w[p + "attn.w_msa.proj.weight"], w[p + "attn.w_msa.proj.bias"],
+                       s["x1"])
+            self._branch(s["x1"], x, keep[0])
+        s["xn2"] = E(n, C)
+        hip.layernorm_rows(s["x1"], w[p + "norm2.weight"], w[p + "norm2.bias"], s["xn2"], self.EPS)
+        s["pre"], s["hid"] = E(n, F), E(n, F)
+        hip.linear(s["xn2"], w[p + "ffn.layers.0.0.weight"], w[p + "ffn.layers.0.0.bias"], s["pre"])
+        hip.gelu(s["pre"], s["hid"])
+        x = E(n, C)
+        if keep is None:
+            hip.linear(s["hid"], w[p + "ffn.layers.1.weight"], w[p + "ffn.layers.1.bias"], x,
+                       res=s["x1"])
+        else:
+            hip.linear(s["hid"], w[p + "ffn.layers.1.weight"], w[p + "ffn.layers.1.bias"], x)
+            self._branch(x, s["x1"], keep[1])
+        return s, x
+
     @torch.no_grad()
     @hip.on_device
     def forward(self, x4, keep=None):
@@ -1276,7 +1312,6 @@ class SwinBackboneGrad(RelationTailGrad):
             raise RuntimeError("x4 must be a [B, h, w, %d] fp32 device tensor" % self.C)
         B, h, wd, C = x4.shape
         n, S, ws, nh = B * h * wd, self.S, self.ws, self.heads
-        F = int(bb.mlp_ratio * C)
         depth = bb.depths[S]
         if keep is not None:
             keep = keep.to(self.dev, torch.float32).contiguous()
@@ -1285,36 +1320,9 @@ class SwinBackboneGrad(RelationTailGrad):
         x = x4.reshape(n, C).clone()
         blocks = []
         for j in range(depth):
-            p = "stages.%d.blocks.%d." % (S, j)
-            s = dict(x=x, shift=0 if j % 2 == 0 else ws // 2)
-            s["xn1"] = E(n, C)
-            hip.layernorm_rows(x, w[p + "norm1.weight"], w[p + "norm1.bias"], s["xn1"], self.EPS)
-            s["qkv"] = E(n, 3 * C)
-            hip.linear(s["xn1"], w[p + "attn.w_msa.qkv.weight"], w[p + "attn.w_msa.qkv.bias"], s["qkv"])
-            s["ao"] = E(n, C)
-            hip.window_attention(s["qkv"], w[p + "attn.w_msa.qkv.bias"],
-                                 w[p + "attn.w_msa.relative_position_bias_table"], s["ao"], B, h, wd,
-                                 C, nh, ws, s["shift"])
-            s["x1"] = E(n, C)
-            if keep is None:
-                hip.linear(s["ao"], w[p + "attn.w_msa.proj.weight"], w[p + "attn.w_msa.proj.bias"],
-                           s["x1"], res=x)
-            else:
-                hip.linear(s["ao"], w[p + "attn.w_msa.proj.weight"], w[p + "attn.w_msa.proj.bias"],
-                           s["x1"])
-                self._branch(s["x1"], x, keep[j, 0])
-            s["xn2"] = E(n, C)
-            hip.layernorm_rows(s["x1"], w[p + "norm2.weight"], w[p + "norm2.bias"], s["xn2"], self.EPS)
-            s["pre"], s["hid"] = E(n, F), E(n, F)
-            hip.linear(s["xn2"], w[p + "ffn.layers.0.0.weight"], w[p + "ffn.layers.0.0.bias"], s["pre"])
-            hip.gelu(s["pre"], s["hid"])
-            x = E(n, C)
-            if keep is None:
-                hip.linear(s["hid"], w[p + "ffn.layers.1.weight"], w[p + "ffn.layers.1.bias"], x,
-                           res=s["x1"])
-            else:
-                hip.linear(s["hid"], w[p + "ffn.layers.1.weight"], w[p + "ffn.layers.1.bias"], x)
-                self._branch(x, s["x1"], keep[j, 1])
+            s, x = self._block_fwd("stages.%d.blocks.%d." % (S, j), x, B, h, wd, C, nh,
+                                   0 if j % 2 == 0 else ws // 2,
+                                   None if keep is None else keep[j])
             blocks.append(s)
         c5 = E(B, h, wd, C)
         hip.layernorm_rows(x, w["norm%d.weight" % S], w["norm%d.bias" % S], c5.view(n, C), self.EPS)
@@ -1339,6 +1347,40 @@ class SwinBackboneGrad(RelationTailGrad):
         hip.scale_rows(out, keep)
         return out
 
+    def _block_bwd(self, p, s, dx, grads, B, h, wd, C, nh, keep):
+        """Backward of `_block_fwd`: dx [B*h*wd, C] the gradient of the block's output rows, `s` its
+        saved tensors; accumulates the block's parameter gradients, returns d of its input rows."""
+        w, E, ws = self.head.w, self._E, self.ws
+        n = B * h * wd
+        hp, wp = -(-h // ws) * ws, -(-wd // ws) * ws
+        nrel = (2 * ws - 1) ** 2
+        a = p + "attn.w_msa."
+        # x_out = x1 + keep * FFN(norm2(x1))
+        dbr = self._scaled(dx, None if keep is None else keep[1])
+        dhid = self._lin_bwd(dbr, s["hid"], w[p + "ffn.layers.1.weight"], grads,
+                             p + "ffn.layers.1.weight", p + "ffn.layers.1.bias")
+        hip.gelu_bwd(dhid, s["pre"], dhid)
+        dxn2 = self._lin_bwd(dhid, s["xn2"], w[p + "ffn.layers.0.0.weight"], grads,
+                             p + "ffn.layers.0.0.weight", p + "ffn.layers.0.0.bias")
+        del dhid
+        dx1 = self._lnr_bwd(dxn2, s["x1"], p + "norm2.", grads, acc=dx)
+        # x1 = x + keep * proj(W-MSA(norm1(x)))
+        dbr = self._scaled(dx1, None if keep is None else keep[0])
+        dao = self._lin_bwd(dbr, s["ao"], w[a + "proj.weight"], grads, a + "proj.weight",
+                            a + "proj.bias")
+        dqkv = E(B * hp * wp, 3 * C)
+        part = E(hip.window_partials_rows(B, h, wd, ws), nh * nrel)
+        hip.window_attention_bwd(s["qkv"], w[a + "qkv.bias"], w[a + "relative_position_bias_table"],
+                                 dao, dqkv, part, B, h, wd, C, nh, ws, s["shift"], out=s["ao"])
+        dtab = E(nh, nrel)
+        hip.colsum(part, dtab.view(-1))
+        hip.transpose(dtab, grads[a + "relative_position_bias_table"])    # -> [(2ws-1)^2, heads]
+        hip.colsum(dqkv, grads[a + "qkv.bias"], accumulate=True)         # padding rows included
+        dq_real = dqkv if (hp, wp) == (h, wd) else \
+            dqkv.view(B, hp, wp, 3 * C)[:, :h, :wd].reshape(n, 3 * C)
+        dxn1 = self._lin_bwd(dq_real, s["xn1"], w[a + "qkv.weight"], grads, a + "qkv.weight", None)
+        return self._lnr_bwd(dxn1, s["x"], p + "norm1.", grads, acc=dx1)
+
     @torch.no_grad()
     @hip.on_device
     def backward(self, d_c5, on_ready=None, need_dx=False):
@@ -1354,39 +1396,217 @@ class SwinBackboneGrad(RelationTailGrad):
         dc = d_c5.to(self.dev, torch.float32).permute(0, 2, 3, 1).contiguous().view(n, C)
         dx = self._lnr_bwd(dc, t["out"], "norm%d." % S, grads)
         ready(self.group_end["norm%d" % S])
-        hp, wp = -(-h // ws) * ws, -(-wd // ws) * ws
-        nrel = (2 * ws - 1) ** 2
         for j in reversed(range(bb.depths[S])):
             p = "stages.%d.blocks.%d." % (S, j)
-            a = p + "attn.w_msa."
-            s = t["blocks"][j]
-            # x_out = x1 + keep * FFN(norm2(x1))
-            dbr = self._scaled(dx, None if keep is None else keep[j, 1])
-            dhid = self._lin_bwd(dbr, s["hid"], w[p + "ffn.layers.1.weight"], grads,
-                                 p + "ffn.layers.1.weight", p + "ffn.layers.1.bias")
-            hip.gelu_bwd(dhid, s["pre"], dhid)
-            dxn2 = self._lin_bwd(dhid, s["xn2"], w[p + "ffn.layers.0.0.weight"], grads,
-                                 p + "ffn.layers.0.0.weight", p + "ffn.layers.0.0.bias")
-            del dhid
-            dx1 = self._lnr_bwd(dxn2, s["x1"], p + "norm2.", grads, acc=dx)
-            # x1 = x + keep * proj(W-MSA(norm1(x)))
-            dbr = self._scaled(dx1, None if keep is None else keep[j, 0])
-            dao = self._lin_bwd(dbr, s["ao"], w[a + "proj.weight"], grads, a + "proj.weight",
-                                a + "proj.bias")
-            dqkv = E(B * hp * wp, 3 * C)
-            part = E(hip.window_partials_rows(B, h, wd, ws), nh * nrel)
-            hip.window_attention_bwd(s["qkv"], w[a + "qkv.bias"], w[a + "relative_position_bias_table"],
-                                     dao, dqkv, part, B, h, wd, C, nh, ws, s["shift"], out=s["ao"])
-            dtab = E(nh, nrel)
-            hip.colsum(part, dtab.view(-1))
-            hip.transpose(dtab, grads[a + "relative_position_bias_table"])    # -> [(2ws-1)^2, heads]
-            hip.colsum(dqkv, grads[a + "qkv.bias"], accumulate=True)         # padding rows included
-            dq_real = dqkv if (hp, wp) == (h, wd) else \
-                dqkv.view(B, hp, wp, 3 * C)[:, :h, :wd].reshape(n, 3 * C)
-            dxn1 = self._lin_bwd(dq_real, s["xn1"], w[a + "qkv.weight"], grads, a + "qkv.weight", None)
-            dx = self._lnr_bwd(dxn1, s["x"], p + "norm1.", grads, acc=dx1)
+            dx = self._block_bwd(p, t["blocks"][j], dx, grads, B, h, wd, C, nh,
+                                 None if keep is None else keep[j])
             ready(self.group_end[p[:-1]])
         ready(self.flat_numel)
         if need_dx:
             return grads, dx.view(B, h, wd, C)
+        return grads
+
+
+class SwinStagesGrad(SwinBackboneGrad):
+    """The Swin backbone with `frozen_stages` in {-1, 0, 1, 2} (configs/deformable_detr/
+    cross_swinb_vg.py:202-226 trains every stage, `frozen_stages=-1`): taped from the IMAGE and
+    differentiated from C2 ... C5 back through every trainable stage, its patch merging and -- with
+    `frozen_stages=-1` -- the patch embedding:
+
+        tape = SwinStagesGrad(swin)
+        c2, c3, c4, c5 = tape.forward(img, keep=None)      # channel-last [B, h, w, C]
+        grads = tape.backward(d_c3, d_c4, d_c5)            # [B, C, h, w] each (d_c2= optional)
+
+    mmdet's `_freeze_stages`: any `frozen_stages >= 0` fixes patch_embed; stages[i - 1] (blocks and
+    downsample) and norm{i - 1} are fixed for 1 <= i <= frozen_stages.  The frozen front runs on the
+    same exact-fp32 kernels without a tape.  Per trainable stage, walking backward: the gradient of
+    the stage's input tokens goes through the patch merging before it -- the reduction Linear
+    (`_lin_bwd`), then `pn_patch_merge_ln_bwd_f32`, which ADDS its dx to the share the stage
+    output's own norm{i} has already written -- then through the stage's blocks in reverse
+    (`_block_bwd`, shared with SwinBackboneGrad).  The patch embedding's weight gradient is
+    dY^T cols over `pn_patch_im2col4_f32`'s rows (the image needs no gradient).
+
+    `keep` [sum(depths), 2, B]: DropPath factors of EVERY block (rates linspace(0, drop_path_rate,
+    sum(depths)) as mmdet); the rows of frozen stages are ignored (mmdet keeps frozen modules in
+    eval mode).  `norm0` is in the layout whenever stage 0 trains but gets a gradient only with
+    `d_c2=` (CrossHead2's loss does not reach C2: `NO_GRAD_GROUPS`)."""
+
+    NO_GRAD_GROUPS = ("norm0",)      # zero gradient unless d_c2 is supplied (TailTrainer: lr 0, wd 0)
+
+    def __init__(self, backbone, flat=None, base=0):
+        nst = len(backbone.depths)
+        f = getattr(backbone, "frozen_stages", -1)
+        if not -1 <= f < nst - 1:
+            raise NotImplementedError("SwinStagesGrad takes frozen_stages in -1 .. %d (%d: "
+                                      "SwinBackboneGrad); got %s" % (nst - 2, nst - 1, f))
+        if tuple(backbone.out_indices) != tuple(range(nst)):
+            raise NotImplementedError("every stage must be an output stage (out_indices=%s)"
+                                      % (tuple(range(nst)),))
+        if backbone.device is None or backbone.device.type != "cuda":
+            raise RuntimeError("SwinStagesGrad needs a backbone on an MI355X (.to('cuda:N'))")
+        if backbone.w is None:
+            backbone._pack()
+        self.head, self.dev, self.t = backbone, backbone.device, None
+        self.S, self.ws, self.first = nst - 1, backbone.ws, max(f, 0)
+        self.train_embed = f < 0
+        self._build_layout(backbone, flat, base)
+
+    @staticmethod
+    def param_groups(backbone):
+        nst = len(backbone.depths)
+        f = getattr(backbone, "frozen_stages", -1)
+        groups = []
+        for i in reversed(range(max(f, 0), nst)):
+            if i < nst - 1:
+                d = "stages.%d.downsample." % i
+                groups.append((d + "reduction", [d + "reduction.weight"]))
+            groups.append(("norm%d" % i, ["norm%d.weight" % i, "norm%d.bias" % i]))
+            if i < nst - 1:
+                groups.append((d + "norm", [d + "norm.weight", d + "norm.bias"]))
+            for j in reversed(range(backbone.depths[i])):
+                p = "stages.%d.blocks.%d." % (i, j)
+                groups.append((p[:-1], [p + n for n in SwinBackboneGrad.BLOCK_PARAMS]))
+        if f < 0:
+            groups.append(("patch_embed", ["patch_embed.norm.weight", "patch_embed.norm.bias",
+                                           "patch_embed.projection.weight",
+                                           "patch_embed.projection.bias"]))
+        return groups
+
+    def stage_input(self):
+        raise NotImplementedError("SwinStagesGrad.forward starts from the image")
+
+    @torch.no_grad()
+    @hip.on_device
+    def forward(self, img, keep=None):
+        bb, w, E = self.head, self.head.w, self._E
+        if not (img.is_cuda and img.dtype == torch.float32 and img.dim() == 4 and img.shape[1] == 3):
+            raise RuntimeError("img must be a [B, 3, H, W] fp32 device tensor")
+        img = img.contiguous()
+        B, _, H, W = img.shape
+        nblk, ws = sum(bb.depths), self.ws
+        if keep is not None:
+            keep = keep.to(self.dev, torch.float32).contiguous()
+            if tuple(keep.shape) != (nblk, 2, B):
+                raise ValueError("keep must be [%d blocks, 2 branches, B=%d]" % (nblk, B))
+        h, wd = -(-H // 4), -(-W // 4)
+        C = bb.num_features[0]
+        n = B * h * wd
+        cols, proj, x = E(n, 64), E(n, C), E(n, C)
+        hip.patch_im2col4(img, cols, B, H, W)
+        hip.linear(cols, w["patch_embed.projection.weight"], w["patch_embed.projection.bias"], proj)
+        hip.layernorm_rows(proj, w["patch_embed.norm.weight"], w["patch_embed.norm.bias"], x, self.EPS)
+        embed = dict(cols=cols, proj=proj) if self.train_embed else None
+        del cols, proj
+        stages, outs, blk0 = [], [], 0
+        for i, (depth, nh) in enumerate(zip(bb.depths, bb.num_heads)):
+            C, n = bb.num_features[i], B * h * wd
+            taped = i >= self.first
+            st = dict(h=h, w=wd, C=C, nh=nh, blk0=blk0, blocks=[])
+            for j in range(depth):
+                kj = keep[blk0 + j] if (keep is not None and taped) else None
+                s, x = self._block_fwd("stages.%d.blocks.%d." % (i, j), x, B, h, wd, C, nh,
+                                       0 if j % 2 == 0 else ws // 2, kj)
+                if taped:
+                    st["blocks"].append(s)
+                del s
+            blk0 += depth
+            c = E(B, h, wd, C)
+            hip.layernorm_rows(x, w["norm%d.weight" % i], w["norm%d.bias" % i], c.view(n, C), self.EPS)
+            outs.append(c)
+            if taped:
+                st["out"] = x
+            if i < self.S:
+                p = "stages.%d.downsample." % i
+                h2, w2 = -(-h // 2), -(-wd // 2)
+                n2 = B * h2 * w2
+                mg, xn = E(n2, 4 * C), E(n2, 2 * C)
+                hip.patch_merge_ln(x, w[p + "norm.weight"], w[p + "norm.bias"], mg, B, h, wd, C, self.EPS)
+                hip.linear(mg, w[p + "reduction.weight"], None, xn)
+                if taped:
+                    st["mg"] = mg                 # the reduction Linear's input (its dW)
+                x, h, wd = xn, h2, w2
+                del mg, xn
+            stages.append(st if taped else None)
+        self.t = dict(B=B, H=H, W=W, stages=stages, embed=embed, keep=keep)
+        return tuple(outs)
+
+    @staticmethod
+    def _unfold_order(g, C):
+        """[..., 4C] neighbour-major ((row*2+col)*C + c, the packed order) -> nn.Unfold order
+        (c*4 + row*2+col, the reference parameter's)."""
+        return g.reshape(*g.shape[:-1], 4, C).transpose(-1, -2).reshape(g.shape)
+
+    def _reduction_bwd(self, i, st, dxin, grads, ready):
+        """Backward of stage i's patch-merging Linear: dxin [n2, 2C] (d of the next stage's input
+        tokens) -> (parameter prefix, d of the merged, normalised rows [n2, 4C])."""
+        w, C = self.head.w, st["C"]
+        p = "stages.%d.downsample." % i
+        # reduction Linear (no bias); the packed weight and hence dW have neighbour-major columns
+        tmp = {"w": torch.zeros(2 * C, 4 * C, device=self.dev, dtype=torch.float32)}
+        dmg = self._lin_bwd(dxin, st["mg"], w[p + "reduction.weight"], tmp, "w", None)
+        grads[p + "reduction.weight"].copy_(self._unfold_order(tmp["w"], C))
+        ready(self.group_end[p + "reduction"])
+        return p, dmg
+
+    def _patch_embed_bwd(self, dx0, grads):
+        """dx0 [B*h*w, C]: d of the patch embedding's output tokens -> its four parameter gradients
+        (the image needs none)."""
+        w, em, C = self.head.w, self.t["embed"], self.head.num_features[0]
+        dproj = self._lnr_bwd(dx0, em["proj"], "patch_embed.norm.", grads)
+        # dW = dY^T cols over the 64-column im2col rows (the last 16 zero) -> [C][3][4][4]
+        tmp = {"w": torch.zeros(C, 64, device=self.dev, dtype=torch.float32),
+               "b": grads["patch_embed.projection.bias"]}
+        self._lin_bwd(dproj, em["cols"], w["patch_embed.projection.weight"], tmp, "w", "b",
+                      need_dx=False)
+        grads["patch_embed.projection.weight"].view(C, 48).copy_(tmp["w"][:, :48])
+
+    @torch.no_grad()
+    @hip.on_device
+    def backward(self, d_c3, d_c4, d_c5, d_c2=None, on_ready=None):
+        """d_c* [B, C, h, w] (any memory format) -> {state-dict name: gradient} (views of the flat
+        buffer, valid until the next backward).  A frozen stage's map gradient is ignored."""
+        if self.t is None:
+            raise RuntimeError("backward() needs a forward() first")
+        bb, w, E, t = self.head, self.head.w, self._E, self.t
+        B, keep = t["B"], t["keep"]
+        ready = on_ready if on_ready is not None else (lambda end: None)
+        grads = self._zero_grads()
+        d_maps = [d_c2, d_c3, d_c4, d_c5]
+        dxin = None                                # d of the tokens entering the stage above
+        for i in reversed(range(self.first, self.S + 1)):
+            st = t["stages"][i]
+            h, wd, C, nh = st["h"], st["w"], st["C"], st["nh"]
+            n = B * h * wd
+            dmg = None
+            if i < self.S:
+                p, dmg = self._reduction_bwd(i, st, dxin, grads, ready)
+            dx = None
+            if d_maps[i] is not None:
+                dc = d_maps[i].to(self.dev, torch.float32).permute(0, 2, 3, 1).contiguous().view(n, C)
+                dx = self._lnr_bwd(dc, st["out"], "norm%d." % i, grads)
+            ready(self.group_end["norm%d" % i])
+            if dmg is not None:
+                acc = dx is not None
+                if not acc:
+                    dx = E(n, C)
+                nb = hip.patch_merge_ln_bwd_nblocks(B, h, wd)
+                part, gb = E(nb, 8 * C), E(8 * C)
+                hip.patch_merge_ln_bwd(dmg, st["out"], w[p + "norm.weight"], dx, part, B, h, wd, C,
+                                       self.EPS, accumulate=acc)
+                hip.colsum(part, gb)
+                grads[p + "norm.weight"].copy_(self._unfold_order(gb[:4 * C], C))
+                grads[p + "norm.bias"].copy_(self._unfold_order(gb[4 * C:], C))
+                ready(self.group_end[p + "norm"])
+            if dx is None:
+                raise ValueError("no gradient reaches stage %d: d_c%d is required" % (i, i + 2))
+            for j in reversed(range(bb.depths[i])):
+                q = "stages.%d.blocks.%d." % (i, j)
+                dx = self._block_bwd(q, st["blocks"][j], dx, grads, B, h, wd, C, nh,
+                                     None if keep is None else keep[st["blk0"] + j])
+                ready(self.group_end[q[:-1]])
+            dxin = dx
+        if self.train_embed:
+            self._patch_embed_bwd(dxin, grads)
+            ready(self.group_end["patch_embed"])
+        ready(self.flat_numel)
         return grads

@@ -140,6 +140,7 @@ _SIGS = {
                                      C.c_uint32, _vp]),
     "pn_layernorm_rows_bwd_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64,
                                             _i32, _f32, _vp]),
+    "pn_patch_merge_ln_bwd_f32": (C.c_int, [_vp] * 5 + [_i32] * 5 + [_f32, _i32, _vp]),
     "pn_gelu_f32": (C.c_int, [_vp, _vp, _i64, _vp]),
     "pn_gelu_bwd_f32": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "pn_window_attention_bwd_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]
@@ -1624,6 +1625,30 @@ def layernorm_rows_bwd(dy, x, gamma, dx, gxhat, eps=1e-5):
     _check(lib().pn_layernorm_rows_bwd_f32(_ptr(dy), lddy, _ptr(x), ldx, _ptr(gamma), _ptr(dx), lddx,
                                            _ptr(gxhat), ldg, rows, Cc, eps, _stream()),
            "pn_layernorm_rows_bwd_f32")
+
+
+def patch_merge_ln_bwd_nblocks(B, H, W):
+    """Workgroups of patch_merge_ln_bwd = rows of its d gamma / d beta partials: four merged rows
+    per workgroup at a time, at most 512 workgroups (2048 waves: two per SIMD of the chip)."""
+    rows = B * (-(-H // 2)) * (-(-W // 2))
+    return max(1, min(-(-rows // 4), 512))
+
+
+def patch_merge_ln_bwd(dy, x, gamma, dx, part, B, H, W, C, eps=1e-5, accumulate=False):
+    """Backward of patch_merge_ln(): dy [B*ceil(H/2)*ceil(W/2)][4C], the saved map x [B*H*W][C],
+    gamma [4C] neighbour-major -> dx [B*H*W][C] (every row written once; `accumulate`: added to)
+    and part [patch_merge_ln_bwd_nblocks(B, H, W)][2][4C] (column-sum it: d gamma | d beta)."""
+    rows = B * (-(-H // 2)) * (-(-W // 2))
+    nblk = patch_merge_ln_bwd_nblocks(B, H, W)
+    for t in (dy, x, gamma, dx, part):
+        assert t.is_contiguous()
+    assert dy.numel() == rows * 4 * C and x.numel() == dx.numel() == B * H * W * C
+    assert gamma.numel() == 4 * C and part.numel() == nblk * 8 * C
+    nbytes = 4.0 * (2 * rows * 4 * C + (2 + bool(accumulate)) * B * H * W * C)
+    _check(_launch("k_patch_merge_ln_bwd", 20.0 * rows * 4 * C, nbytes,
+                   lambda: lib().pn_patch_merge_ln_bwd_f32(
+                       _ptr(dy), _ptr(x), _ptr(gamma), _ptr(dx), _ptr(part), nblk, B, H, W, C, eps,
+                       int(bool(accumulate)), _stream())), "pn_patch_merge_ln_bwd_f32")
 
 
 def gelu(x, out):

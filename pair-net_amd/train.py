@@ -8,8 +8,10 @@ with `train_pixel_decoder` the pixel decoder's encoder path (+5.3 M), with `back
 stages 2-4 (+23.2 M; stem, layer1 and BatchNorm frozen as in the reference's config) -- 53.0 M, the
 reference's whole trainable graph.  With a `SwinTransformerHip` as `backbone=` the last stage and
 its output norm train instead (`SwinBackboneGrad`; `frozen_stages=3` as in
-configs/mask2former/pairnet_swinb.py:220: 25.2 M for Swin-B, 56.7 M for Swin-L).  Without
-`backbone=` the backbone is frozen (a fine-tuning regime).
+configs/mask2former/pairnet_swinb.py:220: 25.2 M for Swin-B, 56.7 M for Swin-L); one whose
+`frozen_stages` is lower trains every stage from there down -- with -1 also every patch merging and
+the patch embedding, as configs/deformable_detr/cross_swinb_vg.py:202-226 does (`SwinStagesGrad`,
+taped from the image).  Without `backbone=` the backbone is frozen (a fine-tuning regime).
 Everything the reference's loss can reach enters through two logits: `loss_r_cls` through
 `rel`, `loss_match` through `importance` (`loss_sub_cls` / `loss_obj_cls` read DETACHED class
 logits, pairnet_head.py:380-390, and train nothing).
@@ -19,7 +21,7 @@ logits, pairnet_head.py:380-390, and train nothing).
 
 Per step: `head.forward` (the inference kernels; hipGraphs if on) -> `head.loss(grads=)` (csrc/
 loss.hip; the two Hungarian assignments on the host as the reference) -> `RelationTailGrad`
-(/ `HeadGrad` / `PixelDecoderGrad` / `BackboneGrad` / `SwinBackboneGrad`) forward-with-tape + backward into one flat
+(/ `HeadGrad` / `PixelDecoderGrad` / `BackboneGrad` / `SwinBackboneGrad` / `SwinStagesGrad`) forward-with-tape + backward into one flat
 gradient buffer -> (world > 1) bucketed all-reduce
 overlapped with the backward pass (`dist.GradReducer`) -> global-norm clip coefficient on the
 device -> ONE AdamW launch over the flat parameter buffer that the head's weight dict aliases ->
@@ -57,9 +59,9 @@ import torch
 from . import hip
 from .dist import GradReducer
 from .grad import (BackboneGrad, FfnDropout, HeadGrad, PixelDecoderGrad, RelationTailGrad,
-                   SwinBackboneGrad)
+                   SwinBackboneGrad, SwinStagesGrad)
 
-__all__ = ["TailTrainer", "step_lr"]
+__all__ = ["TailTrainer", "step_lr", "segment_multipliers"]
 
 
 def step_lr(base_lr, epoch, steps=(5, 10), gamma=0.5):
@@ -68,18 +70,42 @@ def step_lr(base_lr, epoch, steps=(5, 10), gamma=0.5):
     return base_lr * gamma ** sum(1 for s in steps if epoch >= s)
 
 
+def segment_multipliers(names, frozen, lr_mult=None, decay_mult=None, norm_decay_mult=0.0,
+                        swin=False):
+    """Per-segment (lr multipliers, weight-decay multipliers) of the flat parameter buffer, mmcv's
+    `paramwise_cfg`: `lr_mult` / `decay_mult` {substring of a parameter name: multiplier} (a key
+    hit decides alone), `norm_decay_mult` for the head's norms, 0 / 0 for a `frozen` name."""
+    lr_mult, decay_mult = dict(lr_mult or {}), dict(decay_mult or {})
+    lrs, wds = [], []
+    for n in names:
+        lrs.append(0.0 if n in frozen else
+                   next((m for key, m in lr_mult.items() if key in n), 1.0))
+        # (a Swin backbone's names -- norm1 / norm2 / norm3, the bias table -- match none of
+        # these: with a `backbone.` custom key mmcv applies no norm_decay_mult to them)
+        is_norm = ".norms." in n or "post_norm" in n or ".gn." in n
+        assert not (is_norm and swin and n.startswith("backbone.")), n
+        wds.append(0.0 if n in frozen else
+                   next((m for key, m in decay_mult.items() if key in n),
+                        norm_decay_mult if is_norm else 1.0))
+    return lrs, wds
+
+
 class TailTrainer:
     FROZEN_GROUPS = ("cls",)      # cls_embed / post_norm: no gradient in the reference's graph
 
     def __init__(self, head, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  max_norm=0.1, norm_decay_mult=0.0, lr_mult=None, group=None,
                  bucket_bytes=32 << 20, train_decoder=False, train_pixel_decoder=False,
-                 backbone=None, drop_path=False, seed=0, dropout=False, device_targets=False):
+                 backbone=None, drop_path=False, seed=0, dropout=False, device_targets=False,
+                 decay_mult=None):
         """`train_decoder`: also train the nine masked decoder layers, `query_feat`, `query_embed`
         and `level_embed` (`HeadGrad`; the reference's `transformer_decoder` group, lr_mult 0.1 by
         default here as in configs/mask2former/pairnet.py:358-363) -- everything of the head behind
         the pixel decoder.  `lr_mult`: {substring of a parameter name: multiplier} (mmcv's
-        `paramwise_cfg.custom_keys`)."""
+        `paramwise_cfg.custom_keys`).  `decay_mult`: the same for the weight decay (None: 1 for
+        every tensor but the head's norms, as before; {"backbone.": 0.0} is
+        configs/deformable_detr/cross_swinb_vg.py:564).  A key hit decides alone (a rule not pinned
+        to mmcv's, as for `lr_mult`)."""
         self.head = head
         # `device_targets`: loss targets built on the device, a guarded update, no host wait in
         # `step()` (module docstring); default off: the host assignments, launch for launch
@@ -90,7 +116,9 @@ class TailTrainer:
         # A SwinTransformerHip trains its last stage + norm (`SwinBackboneGrad`) at lr_mult 0.01
         # (pairnet_swinb.py:563-571); `drop_path`: mmdet's DropPath on that stage's residual
         # branches at the rates of the backbone's `drop_path_rate`, drawn per step from a host
-        # generator seeded with `seed` (default off: a deterministic step).
+        # generator seeded with `seed` (default off: a deterministic step).  A Swin backbone with
+        # `frozen_stages` below the last stage trains every stage from there down
+        # (`SwinStagesGrad`; DropPath then on every trainable block).
         from .swin import SwinTransformerHip
         self.backbone = backbone
         self.swin = isinstance(backbone, SwinTransformerHip)
@@ -131,7 +159,9 @@ class TailTrainer:
                 backbone.to(dev)
             if backbone.w is None:
                 backbone._pack()
-        bb_cls = SwinBackboneGrad if self.swin else BackboneGrad
+        self.swin_stages = self.swin and backbone.frozen_stages < len(backbone.depths) - 1
+        bb_cls = (SwinStagesGrad if self.swin_stages else SwinBackboneGrad) if self.swin \
+            else BackboneGrad
         n_bb = bb_cls.size_of(backbone) if backbone is not None else 0
         self.flat_grad = torch.zeros(n_head + n_pd + n_bb, device=dev, dtype=torch.float32)
         self.tape = tape = tape_cls(head, flat=self.flat_grad, base=0)
@@ -152,6 +182,9 @@ class TailTrainer:
                 self.layout["backbone." + n] = (o + n_head + n_pd, shape, k)
                 src["backbone." + n] = backbone._params[n]
         frozen = {n for g, names in tape.param_groups(head) if g in self.FROZEN_GROUPS for n in names}
+        if self.swin_stages:      # norm0: the loss does not reach C2 -- no gradient, no decay
+            frozen |= {"backbone." + n for g, names in bb_cls.param_groups(backbone)
+                       if g in bb_cls.NO_GRAD_GROUPS for n in names}
         self.n = n_head + n_pd + n_bb
         self.names = [n for n in self.layout if n not in frozen]
         self._frozen = frozen
@@ -177,18 +210,9 @@ class TailTrainer:
                 # the 1x1 input convolutions: [256,C,1,1] == [256,C])
                 w[n] = view.view(w[n].shape)
         # ---- per-segment multipliers (mmcv paramwise_cfg) ----
-        lr_mult = dict(lr_mult or {})
-        offs, lrs, wds = [], [], []
-        for n in self.layout:
-            o, shape, k = self.layout[n]
-            offs.append(o)
-            lrs.append(0.0 if n in frozen else
-                       next((m for key, m in lr_mult.items() if key in n), 1.0))
-            # (a Swin backbone's names -- norm1 / norm2 / norm3, the bias table -- match none of
-            # these: with a `backbone.` custom key mmcv applies no norm_decay_mult to them)
-            is_norm = ".norms." in n or "post_norm" in n or ".gn." in n
-            assert not (is_norm and self.swin and n.startswith("backbone.")), n
-            wds.append(0.0 if n in frozen else (norm_decay_mult if is_norm else 1.0))
+        offs = [self.layout[n][0] for n in self.layout]
+        lrs, wds = segment_multipliers(self.layout, frozen, lr_mult, decay_mult, norm_decay_mult,
+                                       swin=self.swin)
         offs.append(self.n)
         self.seg_off = torch.tensor(offs, dtype=torch.int64, device=dev)
         self.seg_lr = torch.tensor(lrs, dtype=torch.float32, device=dev)
@@ -296,21 +320,35 @@ class TailTrainer:
             self._refresh_swin() if self.swin else self._refresh_backbone()
 
     def _refresh_swin(self):
-        """Rewrite the Swin backbone's packed weights of the trained stage in place: the bias
-        tables transposed to [heads][(2ws-1)^2], the block GEMMs' bf16-plane splits."""
+        """Rewrite the Swin backbone's packed weights of the trained stages in place, as
+        `SwinTransformerHip._pack` derives them: the bias tables transposed to
+        [heads][(2ws-1)^2], the block GEMMs' bf16-plane splits, the patch-merging norm and
+        reduction weight in neighbour-major column order, the patch-embedding weight in the first
+        48 of its 64 columns."""
         w, p = self.backbone.w, self.params
         for n in self.bb_tape.layout:
-            v = p["backbone." + n]
-            w[n].copy_(v.t() if n.endswith("relative_position_bias_table") else v)
+            v = p.get("backbone." + n)
+            if v is None:                          # (norm0 without a gradient: never moves)
+                continue
+            if n.endswith("relative_position_bias_table"):
+                v = v.t()
+            elif ".downsample." in n:              # nn.Unfold order c*4 + q -> q*C + c
+                c = v.shape[-1] // 4
+                v = v.reshape(*v.shape[:-1], c, 4).transpose(-1, -2).reshape(v.shape)
+            if n == "patch_embed.projection.weight":
+                w[n][:, :48].copy_(v.reshape(v.shape[0], 48))
+            else:
+                w[n].copy_(v)
             if n + ".s3" in w:
                 hip.s3_split(w[n], w[n + ".s3"])
 
     def _drop_path_keep(self, B):
         """mmdet DropPath's per-image scale factors [blocks, 2 branches, B] of the trained stage:
         floor(keep_prob + U[0, 1)) / keep_prob at the block's rate of linspace(0, drop_path_rate,
-        sum(depths))."""
+        sum(depths)).  A `SwinStagesGrad` trainer draws them for all sum(depths) blocks (the tape
+        ignores the rows of frozen stages)."""
         bb = self.backbone
-        S = len(bb.depths) - 1
+        S = 0 if self.swin_stages else len(bb.depths) - 1
         dpr = torch.linspace(0, bb.drop_path_rate, sum(bb.depths), dtype=torch.float64)
         rates = dpr[sum(bb.depths[:S]):].float()                          # [blocks]
         kp = (1.0 - rates).view(-1, 1, 1)
@@ -371,7 +409,10 @@ class TailTrainer:
             # weights: the flat buffers of this trainer no longer back them
             raise RuntimeError("the head (or backbone) re-packed its weights since this TailTrainer "
                                "was built (load_state_dict, parameter update, .to()): build a new one")
-        if self.backbone is not None:
+        if self.swin_stages:                   # the tape runs the whole backbone from the image
+            keep = self._drop_path_keep(feats.shape[0]) if self.drop_path else None
+            feats = [c.permute(0, 3, 1, 2) for c in self.bb_tape.forward(feats, keep)]
+        elif self.backbone is not None:
             feats = [f.clone(memory_format=torch.preserve_format) for f in self.backbone(feats)]
             if self.swin:                      # the taped last stage's C5 feeds the head and loss
                 x4 = self.bb_tape.stage_input()
@@ -410,7 +451,10 @@ class TailTrainer:
         if self.pd_tape is not None:           # back[0]: d memory tokens (HeadGrad)
             npd = self.pd_tape.flat_numel
             dfeats, _ = self.pd_tape.backward(back[0], on_ready=lambda e: self.reducer.ready(nh + e))
-            if self.bb_tape is not None and self.swin:     # d C5; C2-C4 come from frozen stages
+            if self.swin_stages:               # dfeats: d C5, d C4, d C3
+                self.bb_tape.backward(dfeats[2], dfeats[1], dfeats[0],
+                                      on_ready=lambda e: self.reducer.ready(nh + npd + e))
+            elif self.bb_tape is not None and self.swin:   # d C5; C2-C4 come from frozen stages
                 self.bb_tape.backward(dfeats[0], on_ready=lambda e: self.reducer.ready(nh + npd + e))
             elif self.bb_tape is not None:     # dfeats: d C5, d C4, d C3
                 self.bb_tape.forward(feats[0])
