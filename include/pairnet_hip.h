@@ -1346,6 +1346,36 @@ int pn_id_ce_f32(const float* sub, const float* obj, const int64_t* matched, int
                  void* stream);
 
 /* -------------------------------------------------------------------------
+ * The box head's object assignment cost (csrc/box_loss.hip; pair-net_amd/bbox_losses.py drives it):
+ * `self.bbox_assigner.assign(bbox_pred, cls_score, gt_bboxes, gt_labels, img_metas, ...)` at
+ * pairnet_bbox_head.py:863-865 -- [3P] mmdet HungarianAssigner under configs/deformable_detr/
+ * cross_r101_vg.py:158-163 (FocalLossCost 2.0, BBoxL1Cost 5.0 xywh, IoUCost giou 2.0) -- for every
+ * image of the batch in one launch, laid out as pn_lsa_f32's table wants.  Entry added at ABI 34
+ * (adding entries is compatible).
+ *   cls [B][Q][nc] the kept queries' class logits, box [B][Q][4] cxcywh normalised;
+ *   gt_labels [labels_len] int64 and gt_bboxes [boxes_len][4] fp32 (xyxy, pixels): the batch's
+ *   concatenated ground truth; factor [B][4] = (img_w, img_h, img_w, img_h) of `img_shape`;
+ *   tab [B][4] int64 on the device = {offset of the image's row-major Q x G block in cost, G, offset
+ *   of its labels in gt_labels, offset of its boxes in gt_bboxes (in boxes)}.
+ * For query q and ground truth g, in fp32 and in this order, without fused multiply-adds:
+ *   p        = sigmoid(cls[q][label_g])
+ *   cls_cost = ((-log(p + eps)) alpha (1 - p)^gamma - (-log((1 - p) + eps)) (1 - alpha) p^gamma) w_cls
+ *   reg_cost = (sum_i |box[q][i] - cxcywh(gt_g / factor)[i]|) w_reg
+ *   iou_cost = (-GIoU(xyxy(box[q]) * factor, gt_g)) w_iou      (mmdet bbox_overlaps: union and
+ *              enclosing area clamped to >= iou_eps)
+ *   cost     = (cls_cost + reg_cost) + iou_cost
+ * One cell per lane, no atomics, bitwise reproducible.  max_cells: the largest Q * G of the table,
+ * known from shapes (sizes the grid; cells past it are not written).  A table row outside a buffer
+ * or with G outside [1, 1024] leaves its block untouched; a label outside [0, nc) gives a NaN cell
+ * (pn_lsa_f32 status 1); a NaN operand gives a NaN cell.  2 <= Q <= 1024, nc <= 256. */
+int pn_box_match_cost_f32(const float* cls, const float* box, const int64_t* gt_labels,
+                          int64_t labels_len, const float* gt_bboxes, int64_t boxes_len,
+                          const float* factor, const int64_t* tab, float* cost, int64_t cost_len,
+                          int64_t max_cells, int B, int Q, int nc, float w_cls, float w_reg,
+                          float w_iou, float alpha, float gamma, float eps, float iou_eps,
+                          void* stream);
+
+/* -------------------------------------------------------------------------
  * Backward of the mask logits (csrc/seg_grad.hip): the two products that differentiate
  *   mask_pred = torch.einsum("bqc,bchw->bqhw", mask_embed, mask_feature)
  * (pairnet_head.py:236-243 / baseline.py:254-296, once per decoder layer) from the COMPACT gradient

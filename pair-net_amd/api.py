@@ -12,10 +12,12 @@ from .neck import ChannelMapper  # noqa: F401
 from .head import CrossHead2  # noqa: F401
 from .pipeline import PipelinedHead  # noqa: F401
 from .grad import (BackboneGrad, FfnDropout, HeadGrad, PixelDecoderGrad,  # noqa: F401
-                   RelationTailGrad, SwinBackboneGrad, SwinStagesGrad)
+                   RelationTailGrad, SwinBackboneGrad, SwinStagesGrad, BBoxTailGrad)
 from .seg_grad import BaselineHeadGrad, SegmenterHeadGrad, SegPixelDecoderGrad  # noqa: F401
 from .train import TailTrainer  # noqa: F401
 from .baseline_train import BaselineTrainer  # noqa: F401
+from .bbox_train import BBoxTrainer  # noqa: F401
+from .bbox_losses import CrossHeadBBoxLoss  # noqa: F401
 from .seg_losses import Mask2FormerLoss  # noqa: F401
 from .baseline_losses import BaselineRelationLoss  # noqa: F401
 from .preprocess import TestPipeline  # noqa: F401
@@ -35,4 +37,4 @@ __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "Cros
            "CrossHeadBBox", "ChannelMapper", "bbox_head_cfg", "channel_mapper_cfg", "cross_r101_vg",
            "TripletEvaluator", "SceneGraphMetrics", "StreamingEvaluator", "PanopticQuality", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "SwinStagesGrad", "SegmenterHeadGrad", "BaselineHeadGrad", "SegPixelDecoderGrad", "TailTrainer", "BaselineTrainer", "FfnDropout",
            "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg", "Mask2FormerLoss",
-           "BaselineRelationLoss"]
+           "BaselineRelationLoss", "BBoxTailGrad", "BBoxTrainer", "CrossHeadBBoxLoss"]

@@ -43,7 +43,8 @@ from .head import CrossHead2, _decoder_param_shapes
 
 
 class CrossHeadBBox(CrossHead2):
-    """Drop-in for the reference's `CrossHeadBBox` (inference half)."""
+    """Drop-in for the reference's `CrossHeadBBox`: inference, `loss` / `val_losses`
+    (bbox_losses.py) and, through `pairnet_amd.BBoxTrainer` (bbox_train.py), the training step."""
 
     _pair_masks_fusable = False      # (CrossHead2.fused_pair_masks: not for this head)
 
@@ -61,8 +62,6 @@ class CrossHeadBBox(CrossHead2):
         if transformer is None:
             raise ValueError("CrossHeadBBox needs `transformer=` (the reference class builds "
                              "its trunk from it, pairnet_bbox_head.py:66)")
-        if train_cfg:
-            raise NotImplementedError("inference path only (SURVEY.md section 8)")
         transformer = ConfigDict(transformer)
         relation_decoder = ConfigDict(relation_decoder)
         if not (as_two_stage and with_box_refine and transformer.get("as_two_stage", False)):
@@ -102,7 +101,12 @@ class CrossHeadBBox(CrossHead2):
         self.dec_ffn = dec.transformerlayers.get("feedforward_channels", 1024)
         self.num_rel_layers = relation_decoder.num_layers
         self.rel_ffn = relation_decoder.transformerlayers.ffn_cfgs.feedforward_channels
-        self.test_cfg, self.train_cfg = test_cfg, None
+        self.test_cfg, self.train_cfg = test_cfg, train_cfg
+        # (checked when the loss is first built: bbox_losses.py refuses what it does not cover)
+        self._loss_cfg = dict(train_cfg=train_cfg, rel_cls_loss=rel_cls_loss,
+                              subobj_cls_loss=subobj_cls_loss,
+                              importance_match_loss=importance_match_loss)
+        self._loss = None
         if self.num_levels != 4 or self.num_proposals > 512 or self.num_proposals < self.KEPT \
                 or self.cls_out_channels > 256 or num_rel_query > 128:
             raise NotImplementedError("4 levels, <= 512 proposals, <= 256 classes")
@@ -738,6 +742,38 @@ class CrossHeadBBox(CrossHead2):
 
     def forward_head(self, *a, **k):
         raise NotImplementedError("CrossHeadBBox has no forward_head (pairnet_bbox_head.py)")
+
+    # -------------------------------------------------------------------- loss
+    def loss(self, all_cls_scores, all_bbox_preds, gt_rels_list, gt_bboxes_list, gt_labels_list,
+             img_metas, gt_bboxes_ignore=None, **kw):
+        """The reference's `CrossHeadBBox.loss` (pairnet_bbox_head.py:362-464): {loss_r_cls,
+        loss_sub_cls, loss_obj_cls, loss_match} as 0-dim device tensors from the two dicts
+        `forward` returns and the per-image ground truth (bbox_losses.py; `grads={}` receives the
+        logit gradients, `device_targets=True` builds the targets without a host wait)."""
+        if self._loss is None:
+            from .bbox_losses import CrossHeadBBoxLoss
+            self._loss = CrossHeadBBoxLoss(self.num_classes, self.num_relations, self.num_rel_query,
+                                           **self._loss_cfg)
+        return self._loss.loss(all_cls_scores, all_bbox_preds, gt_rels_list, gt_bboxes_list,
+                               gt_labels_list, img_metas, gt_bboxes_ignore=gt_bboxes_ignore, **kw)
+
+    def forward_train(self, *a, **kw):
+        raise NotImplementedError(
+            "forward_train + autograd is not how this head trains: `val_losses()` / `loss()` give "
+            "the reference's loss values, `loss(..., grads={})` their gradients w.r.t. the logits, "
+            "and `pairnet_amd.BBoxTrainer(head).step(...)` runs one iteration")
+
+    def val_losses(self, x, img_metas, gt_rels, gt_bboxes, gt_labels=None, gt_masks=None,
+                   gt_bboxes_ignore=None, **kw):
+        """The values of the reference's `forward_train` (pairnet_bbox_head.py:968-1006):
+        `outs = self(x, img_metas)`, then `loss(*outs, gt_rels, gt_bboxes, gt_labels, img_metas)`.
+        Forward only (`gt_masks` is accepted and, as in the reference, not read)."""
+        if gt_labels is None:
+            raise ValueError("gt_labels is required (the reference's three-argument form feeds "
+                             "loss() one positional argument short)")
+        outs = self.forward(x, img_metas)
+        return self.loss(*outs, gt_rels, gt_bboxes, gt_labels, img_metas,
+                         gt_bboxes_ignore=gt_bboxes_ignore, **kw)
 
     # ------------------------------------------------------- post-processing
     @torch.no_grad()

@@ -416,10 +416,11 @@ class PSGTr:
         if head_type not in heads:
             raise NotImplementedError("bbox_head.type must be one of %s" % sorted(heads))
         # (mmdet's SingleStageDetector hands the model-level train_cfg to the head -- the
-        # base class psgtr.py:84-86 calls; here only
-        # CrossHead2 reads it, for the forward values of its loss)
+        # base class psgtr.py:84-86 calls; here
+        # CrossHead2 and CrossHeadBBox read it, for their losses)
         self.bbox_head = heads[head_type](**head_cfg,
-                                          train_cfg=train_cfg if head_type == "CrossHead2" else None,
+                                          train_cfg=train_cfg if head_type in (
+                                              "CrossHead2", "CrossHeadBBox") else None,
                                           test_cfg=test_cfg or dict(max_per_img=100))
         self.num_classes = self.bbox_head.num_classes
         self.test_pipeline = None     # built by detect() (or set a preprocess.TestPipeline)
@@ -722,6 +723,58 @@ class PSGTr:
         loss = sum(v for k, v in out.items() if "loss" in k)
         return dict(loss=loss, log_vars={k: float(v) for k, v in list(out.items()) + [("loss", loss)]},
                     num_samples=len(img_metas))
+
+    def box_trainer(self, **kw):
+        """`trainer()` for the box head: builds and keeps a `pairnet_amd.BBoxTrainer` over the
+        parameters the reference's `losses.backward()` reaches behind a `CrossHeadBBox` -- the
+        relation tail; the trunk, neck and backbone are detached in the reference's graph
+        (bbox_train.py).  Keywords go to `BBoxTrainer` (lr, max_norm, lr_mult,
+        decay_mult, device_targets).  `trainer()`, `train_step()` and `val_losses()` keep refusing
+        this head."""
+        from .bbox_train import BBoxTrainer
+        if type(self.bbox_head) is not CrossHeadBBox:
+            raise NotImplementedError("box_trainer is built for CrossHeadBBox only (%s: trainer() / "
+                                      "full_trainer())" % type(self.bbox_head).__name__)
+        self._box_trainer = BBoxTrainer(self.bbox_head, **kw)
+        return self._box_trainer
+
+    def box_train_step(self, img, img_metas=None, gt_rels=None, gt_bboxes=None, gt_labels=None):
+        """`train_step` for the box head, the same two call forms: `forward_train`'s argument
+        order (pairnet_bbox_head.py:968-978) -> the four loss terms + `grad_norm` (+
+        `assign_status` for a `device_targets` trainer), device scalars; or `(data_batch,
+        optimizer)` -> mmdet's dict(loss, log_vars, num_samples).  Backbone and neck run as in
+        inference (frozen: the reference's graph does not reach them), then `box_trainer().step`
+        -- the trainer an earlier `box_trainer(...)` call built if there is one."""
+        mmdet_form = isinstance(img, dict)
+        if mmdet_form:
+            data = img
+            unwrap = lambda v: getattr(v, "data", v)        # (mmcv DataContainer)
+            first = lambda v: v[0] if isinstance(v, (list, tuple)) and len(v) == 1 and \
+                isinstance(v[0], (list, tuple)) else v
+            img = unwrap(data["img"])
+            if isinstance(img, (list, tuple)):
+                img = img[0]
+            img_metas = first(unwrap(data["img_metas"]))
+            gt_rels, gt_labels = first(unwrap(data["gt_rels"])), first(unwrap(data["gt_labels"]))
+            gt_bboxes = first(unwrap(data["gt_bboxes"]))
+        tr = getattr(self, "_box_trainer", None) or self.box_trainer()
+        out = tr.step(self.extract_feat(img), img_metas, gt_rels, gt_bboxes, gt_labels)
+        if not mmdet_form:
+            return out
+        loss = sum(v for k, v in out.items() if "loss" in k)
+        return dict(loss=loss, log_vars={k: float(v) for k, v in list(out.items()) + [("loss", loss)]},
+                    num_samples=len(img_metas))
+
+    @torch.no_grad()
+    def val_box_losses(self, img, img_metas, gt_rels, gt_bboxes, gt_labels, **kw):
+        """The values of the reference's `forward_train` behind a `CrossHeadBBox`
+        (psgtr.py:113-146 -> pairnet_bbox_head.py:968-1006): extract_feat -> head forward ->
+        `loss`.  Forward only; keywords go to `CrossHeadBBox.loss` (`grads={}`,
+        `device_targets=True`)."""
+        if type(self.bbox_head) is not CrossHeadBBox:
+            raise NotImplementedError("val_box_losses is built for CrossHeadBBox only")
+        return self.bbox_head.val_losses(self.extract_feat(img), img_metas, gt_rels, gt_bboxes,
+                                         gt_labels, **kw)
 
     @torch.no_grad()
     def detect(self, image, rescale=False):

@@ -33,7 +33,7 @@ import torch
 from . import hip
 
 __all__ = ["RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad",
-           "SwinStagesGrad", "FfnDropout"]
+           "SwinStagesGrad", "FfnDropout", "BBoxTailGrad"]
 
 
 class FfnDropout(namedtuple("FfnDropout", "p seed subseq step layer")):
@@ -1610,3 +1610,121 @@ class SwinStagesGrad(SwinBackboneGrad):
             ready(self.group_end["patch_embed"])
         ready(self.flat_numel)
         return grads
+
+
+class BBoxTailGrad(RelationTailGrad):
+    """The relation tail of `CrossHeadBBox` (bbox_head.py), taped: what `losses.backward()` reaches
+    in the reference's box head.  pairnet_bbox_head.py:261 detaches the trunk's queries
+    (`query_feats = hs.clone().detach()`) and :322-330 the class logits, so the graph holds
+    `sub_query_update` / `obj_query_update`, `update_importance`, the six `relation_decoder`
+    layers, `rel_query_feat`, `rel_query_pos_embed`, `rel_key_pos_embed` and `rel_cls_embed` --
+    `CrossHead2`'s tail under other parameter names.
+
+        tape = BBoxTailGrad(head); out = tape.forward(pl.q, pl.cls, pl.sub_pos, pl.obj_pos)
+        _, grads = tape.backward(g_rel=..., g_importance=...)
+
+    Starts from the plan's kept, detached query rows `pl.q` [B * 100, 256] and takes the kept class
+    logits `pl.cls` as given: no `post_norm` / `cls_embed`, no class group in the layout.  The
+    layout carries the reference's names; `rel_value_pos_embed` (dead weight) and the trunk get no
+    gradient and are not in it.  d q is dropped (`backward` returns None in its place)."""
+
+    # CrossHead2's names of the two embeddings (what the inherited kernels' composition writes to,
+    # and what `CrossHeadBBox._pack` aliases in the weight dict) -> the reference's
+    ALIASES = OrderedDict((("rel_query_embed.weight", "rel_query_pos_embed.weight"),
+                           ("rel_query_embed2.weight", "rel_key_pos_embed.weight")))
+
+    @staticmethod
+    def param_groups(head):
+        alias = BBoxTailGrad.ALIASES
+        return [(g, [alias.get(n, n) for n in names])
+                for g, names in RelationTailGrad.param_groups(head) if g != "cls"]
+
+    def _zero_grads(self):
+        self.flat_grad.zero_()
+        grads = dict(self.grads)
+        for a, n in self.ALIASES.items():
+            grads[a] = self.grads[n]
+        return grads
+
+    def _lin_bwd(self, dy, x, W, grads, wname, bname, row0=0, need_dx=True):
+        """`rel_cls_embed` has num_relations rows (50 on Visual Genome): the GEMMs contract over
+        multiples of 4, so an output width that is none is padded with zero columns / rows, as
+        `_cls_backward` pads the class logits."""
+        N, K = W.shape
+        if N % 4 == 0:
+            return super()._lin_bwd(dy, x, W, grads, wname, bname, row0, need_dx)
+        Np, M = (N + 3) // 4 * 4, dy.shape[0]
+        zeros = lambda *s: torch.zeros(*s, device=self.dev, dtype=torch.float32)
+        dyp, Wp = zeros(M, Np), zeros(Np, K)
+        dyp[:, :N].copy_(dy)
+        Wp[:N].copy_(W)
+        gp = {"W": zeros(Np, K), "b": zeros(Np)}
+        dx = super()._lin_bwd(dyp, x, Wp, gp, "W", None if bname is None else "b", 0, need_dx)
+        self._acc(grads[wname][row0:row0 + N], gp["W"][:N])
+        if bname is not None:
+            self._acc(grads[bname][row0:row0 + N], gp["b"][:N])
+        return dx
+
+    @torch.no_grad()
+    @hip.on_device
+    def forward(self, q, cls, sub_pos=None, obj_pos=None, dropout=None):
+        """q [B * 100, 256], cls [B, 100, nc] (the kept queries and their class logits, both
+        detached in the reference) -> dict(rel, importance, importance_raw, sub, obj, cls, sub_pos,
+        obj_pos); the pair list is the top-k of `importance` unless `sub_pos` / `obj_pos` are given."""
+        head, w, E = self.head, self.head.w, self._E
+        Q, R = self.Q, self.R
+        if not (q.is_cuda and q.dtype == torch.float32 and q.dim() == 2 and q.shape[1] == 256
+                and q.is_contiguous() and q.shape[0] % Q == 0):
+            raise RuntimeError("q must be a contiguous [B * Q, 256] fp32 device tensor")
+        B = q.shape[0] // Q
+        if cls.dim() != 3 or tuple(cls.shape[:2]) != (B, Q) or not cls.is_contiguous():
+            raise RuntimeError("cls must be a contiguous [B, Q, nc] fp32 device tensor")
+        nc = cls.shape[2]
+        t = self.t = dict(B=B, q=q)
+        # ---- Pair Proposal Network (pairnet_bbox_head.py:268-279) ----
+        for side in ("sub", "obj"):
+            mlp = side + "_query_update"
+            h1, h2, e = E(B * Q, 256), E(B * Q, 256), E(B * Q, 256)
+            hip.linear(q, w[mlp + ".0.weight"], w[mlp + ".0.bias"], h1, relu=True)
+            hip.linear(h1, w[mlp + ".2.weight"], w[mlp + ".2.bias"], h2, relu=True)
+            hip.linear(h2, w[mlp + ".4.weight"], w[mlp + ".4.bias"], e)
+            t[side] = (h1, h2, e)
+        ml = "update_importance.conv_layers."
+        raw, c1, c2, imp = E(B, Q, Q), E(B, Q, Q, 64), E(B, Q, Q, 64), E(B, Q, Q)
+        hip.ppn_front(t["sub"][2], t["obj"][2], w[ml + "0.0.weight"], w[ml + "0.0.bias"], raw, c1,
+                      B, Q)
+        hip.conv2d_ex(c1, w[ml + "1.0.weight"], w[ml + "1.0.bias"], None, c2, B, Q, Q, 64, 64, 7,
+                      7, 1, 3, relu=True)
+        hip.mlearner_last(c2, w[ml + "2.0.weight"], w[ml + "2.0.bias"], imp, B, Q)
+        t.update(raw=raw, c1=c1, c2=c2)
+        i64 = lambda *s: torch.empty(*s, device=self.dev, dtype=torch.int64)
+        pair_idx = i64(B, 2 * R)
+        if sub_pos is None:
+            topk, sub_pos, obj_pos = i64(B, R), i64(B, R), i64(B, R)
+            hip.topk_pairs(imp, topk, sub_pos, obj_pos, B, Q, R, pair=pair_idx)
+        else:
+            sub_pos = sub_pos.to(self.dev, torch.int64).contiguous()
+            obj_pos = obj_pos.to(self.dev, torch.int64).contiguous()
+            pair_idx[:, :R].copy_(sub_pos)
+            pair_idx[:, R:].copy_(obj_pos)
+        t.update(sub_pos=sub_pos, obj_pos=obj_pos, pair_idx=pair_idx)
+        # ---- pair features and the relation decoder (:281-320) ----
+        pair = E(B * 2 * R, 256)
+        hip.gather_rows(q, pair_idx, pair, B, Q, 2 * R, 256)
+        rel = self._relation_forward(pair, B, dropout)
+        sub, obj = E(B, R, nc), E(B, R, nc)
+        hip.gather_rows(cls, sub_pos, sub, B, Q, R, nc)
+        hip.gather_rows(cls, obj_pos, obj, B, Q, R, nc)
+        return dict(rel=rel, importance=imp, importance_raw=raw, sub=sub, obj=obj, cls=cls,
+                    sub_pos=sub_pos, obj_pos=obj_pos)
+
+    @torch.no_grad()
+    @hip.on_device
+    def backward(self, g_rel=None, g_importance=None, on_ready=None):
+        """-> (None, {reference parameter name: gradient}).  The class logits are detached
+        (pairnet_bbox_head.py:322-330): `loss_sub_cls` / `loss_obj_cls` reach no parameter, so
+        their logit gradients are not taken.  The gradients are views of `self.flat_grad`."""
+        self._backward_tail(g_rel, g_importance, None, None, True, on_ready)
+        if on_ready is not None:
+            on_ready(self.flat_numel)
+        return None, self.grads

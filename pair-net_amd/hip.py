@@ -246,6 +246,8 @@ _SIGS = {
                                  _vp, _vp, _vp, _vp]),
     "pn_id_ce_f32": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _f32, _vp,
                                _vp, _vp, _vp, _vp]),
+    "pn_box_match_cost_f32": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64,
+                                        _i32, _i32, _i32] + [_f32] * 7 + [_vp]),
     "pn_mask_grad_kslice": (C.c_int, []),
     "pn_mask_embed_grad_scratch_floats": (_i64, [_i32, _i64]),
     "pn_mask_embed_grad_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _i64,
@@ -1920,6 +1922,25 @@ def id_ce(sub, obj, matched, tab, pos, w_s, w_o, row_loss, out, g_sub=None, g_ob
                               _ptr(tab, torch.int64), _ptr(pos, torch.int32), pos.shape[0], B, R, Q,
                               w_s, w_o, _ptr(row_loss), _ptr(out), _ptr(g_sub), _ptr(g_obj),
                               _stream()), "pn_id_ce_f32")
+
+
+# ---- the box head's object assignment cost (csrc/box_loss.hip; composed in bbox_losses.py) --------
+def box_match_cost(cls, box, gt_labels, gt_bboxes, factor, tab, cost, max_cells, w_cls=2.0,
+                   w_reg=5.0, w_iou=2.0, alpha=0.25, gamma=2.0, eps=1e-12, iou_eps=1e-6):
+    """include/pairnet_hip.h: every image's [Q, G_b] box match cost block of the flat `cost`, one
+    launch.  cls [B, Q, nc], box [B, Q, 4] (cxcywh, normalised), factor [B, 4] fp32; gt_labels [.]
+    int64 and gt_bboxes [., 4] fp32 (xyxy, pixels) concatenated over the batch; tab [B, 4] int64 =
+    (cost offset, G, label offset, box offset); `max_cells`: the largest Q * G_b."""
+    B, Q, nc = cls.shape
+    assert box.shape == (B, Q, 4) and factor.shape == (B, 4) and tab.shape == (B, 4)
+    assert gt_bboxes.dim() == 2 and gt_bboxes.shape[1] == 4 and gt_labels.dim() == 1
+    assert all(t.is_contiguous() for t in (cls, box, gt_labels, gt_bboxes, factor, tab, cost))
+    _check(lib().pn_box_match_cost_f32(_ptr(cls), _ptr(box), _ptr(gt_labels, torch.int64),
+                                       gt_labels.numel(), _ptr(gt_bboxes), gt_bboxes.shape[0],
+                                       _ptr(factor), _ptr(tab, torch.int64), _ptr(cost),
+                                       cost.numel(), int(max_cells), B, Q, nc, w_cls, w_reg, w_iou,
+                                       alpha, gamma, eps, iou_eps, _stream()),
+           "pn_box_match_cost_f32")
 
 
 # ---- the mask logits' backward (csrc/seg_grad.hip; composed in seg_grad.py) -----------------------
