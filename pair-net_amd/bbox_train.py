@@ -19,11 +19,11 @@ Per step:
      kernels, eval mode, no tape; the backbone and neck run before it (`PSGTr.box_train_step`);
   2. `BBoxTailGrad.forward` from the kept, detached queries `pl.q` and class logits `pl.cls`;
   3. `head.loss(..., grads=)` (bbox_losses.py: `pn_box_match_cost_f32`, the two assignments);
-  4. the tape's backward into one flat gradient buffer;
-  5. global-norm clip (`max_norm`, default 0.1; cross_r101_vg.py:324 itself sets 0.01);
-  6. ONE AdamW launch over the flat parameter buffer that the head's weight dict aliases --
-     `device_targets=True`: the guarded launch behind `assign_status`, no host wait in `step()`;
-  7. refresh of the derived packs `CrossHeadBBox._pack` builds for the relation stage.
+  4. the tape's backward into the flat gradient buffer;
+  5. `FlatTrainer.apply_gradients` (flat_trainer.py, which also owns the buffers and their
+     set-up): global-norm clip (`max_norm`, default 0.1; cross_r101_vg.py:324 itself sets 0.01),
+     ONE AdamW launch -- `device_targets=True`: the guarded launch behind `assign_status`, no
+     host wait in `step()` -- and the refresh of the relation stage's derived packs.
 
 DETERMINISTIC.  The reference runs the trunk in train mode, so its 0.1 dropouts (the decoder's
 self-attention and every FFN of the trunk, cross_r101_vg.py:41-80) are drawn even though nothing
@@ -35,22 +35,21 @@ Out of scope: the one-stage / no-refine trunk, the RMSNorm / SwiGLU decoder of
 `pairnet_r101_vg.py` and its MultilabelFocalLoss, the commented-out detection losses, a
 data-parallel `group=` step, training the trunk, neck or backbone (the graph does not reach them).
 """
-from collections import OrderedDict
-
 import torch
 
 from . import hip
 from . import plans
 from .dist import GradReducer
+from .flat_trainer import (MATRIX_LEARNER_REPACKED, FlatTrainer, refresh_matrix_learner, refresh_r0,
+                           refresh_relation_cross_attention, refresh_self_attention)
 from .grad import BBoxTailGrad
-from .train import TailTrainer, segment_multipliers
+from .train import segment_multipliers
 
 __all__ = ["BBoxTrainer"]
 
 
-class BBoxTrainer(TailTrainer):
-    """`TailTrainer`'s flat buffers, clip, AdamW launch, derived-pack refresh and `write_back`
-    around `BBoxTailGrad` (module docstring)."""
+class BBoxTrainer(FlatTrainer):
+    """`FlatTrainer` around `BBoxTailGrad` (module docstring); nothing in its layout is frozen."""
 
     def __init__(self, head, lr=2e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  max_norm=0.1, norm_decay_mult=0.0, lr_mult=None, decay_mult=None,
@@ -59,53 +58,25 @@ class BBoxTrainer(TailTrainer):
         if not isinstance(head, CrossHeadBBox):
             raise TypeError("BBoxTrainer trains a CrossHeadBBox (TailTrainer: CrossHead2, "
                             "BaselineTrainer: CrossHeadBaseline)")
-        self.head = head
         self.device_targets = bool(device_targets)
-        self.backbone, self.swin, self.swin_stages, self.drop_path = None, False, False, False
-        self.drop_p, self.train_decoder, self.train_pixel_decoder = 0.0, False, False
-        self.pd_tape = self.bb_tape = None
         if head.device is None or head.device.type != "cuda":
             raise RuntimeError("BBoxTrainer needs a head on an MI355X (.to('cuda:N'))")
-        if head.w is None:
-            head._pack()
-        # plans captured so far bake the addresses of the weight tensors that are re-homed below
-        # into their hipGraphs: start from fresh plans (the arenas, shape-dependent only, stay)
-        head._plans = plans.PlanCache(head._plans.max_plans)
-        dev = self.dev = head.device
-        self.n = BBoxTailGrad.size_of(head)
-        self.flat_grad = torch.zeros(self.n, device=dev, dtype=torch.float32)
-        self.tape = tape = BBoxTailGrad(head, flat=self.flat_grad, base=0)
-        self.lr, self.wd, self.betas, self.eps, self.max_norm = lr, weight_decay, betas, eps, max_norm
-        self.layout = OrderedDict(tape.layout)
-        self.names, self._frozen = list(self.layout), set()
-        # ---- flat parameters; the head's device weights become views of them ----
-        self.flat_p = torch.zeros(self.n, device=dev, dtype=torch.float32)
-        self.flat_m = torch.zeros_like(self.flat_p)
-        self.flat_v = torch.zeros_like(self.flat_p)
-        w = head.w
-        self.params = OrderedDict()
-        ml = "update_importance.conv_layers."
-        self._repacked = {ml + "1.0.weight", ml + "2.0.weight"}   # w[...] holds another layout
-        for n, (o, shape, k) in self.layout.items():
-            view = self.flat_p[o:o + k].view(shape)
-            view.copy_(head._params[n].to(dev))
-            self.params[n] = view
-            if n not in self._repacked:
-                w[n] = view.view(w[n].shape)
-        for alias, n in BBoxTailGrad.ALIASES.items():   # CrossHead2's names of the relation stage
-            w[alias] = w[n]
-        offs = [o for o, _, _ in self.layout.values()] + [self.n]
-        lrs, wds = segment_multipliers(self.layout, self._frozen, lr_mult, decay_mult,
-                                       norm_decay_mult)
-        self.seg_off = torch.tensor(offs, dtype=torch.int64, device=dev)
-        self.seg_lr = torch.tensor(lrs, dtype=torch.float32, device=dev)
-        self.seg_wd = torch.tensor(wds, dtype=torch.float32, device=dev)
-        self.clip = torch.zeros(2, device=dev, dtype=torch.float32)     # [grad norm, coefficient]
-        self._scratch = torch.zeros(256, device=dev, dtype=torch.float64)
+        super().__init__(
+            head, [("tape", "", BBoxTailGrad, head)],
+            lambda names, frozen: segment_multipliers(names, frozen, lr_mult, decay_mult,
+                                                      norm_decay_mult),
+            lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_norm=max_norm,
+            repacked=MATRIX_LEARNER_REPACKED,
+            aliases=BBoxTailGrad.ALIASES)       # CrossHead2's names of the relation stage
         self.reducer = GradReducer(self.flat_grad, group=None)
-        self.steps = 0
-        self._w_dicts = (head.w, None)
-        self._refresh_derived()
+
+    def _refresh_derived(self):
+        """The packs `CrossHeadBBox._pack` builds for the relation stage."""
+        head, w, p = self.head, self.head.w, self.params
+        refresh_self_attention(head, w, p, "relation_decoder", head.num_rel_layers, 1)
+        refresh_relation_cross_attention(head, w, p)
+        refresh_matrix_learner(head, w, p)
+        refresh_r0(head, w, p)
 
     def _trunk(self, feats, img_metas):
         """Step 1: the inference kernels up to `_select` -> the plan (pl.q, pl.cls, pl.box)."""
@@ -130,9 +101,7 @@ class BBoxTrainer(TailTrainer):
         `device_targets` trainer, `assign_status` (device int32 scalar; non-zero: the batch's cost
         matrices were refused and the update was skipped on the device)."""
         head, tape = self.head, self.tape
-        if head.w is not self._w_dicts[0]:
-            raise RuntimeError("the head re-packed its weights since this BBoxTrainer was built "
-                               "(load_state_dict, parameter update, .to()): build a new one")
+        self._check_not_repacked()
         pl = self._trunk(feats, img_metas)
         out = tape.forward(pl.q, pl.cls)
         up = {}
@@ -141,7 +110,7 @@ class BBoxTrainer(TailTrainer):
                            gt_bboxes, gt_labels, img_metas, grads=up,
                            device_targets=self.device_targets)
         self.reducer.start()
-        tape.backward(g_rel=up["rel"], g_importance=up["importance"], on_ready=self.reducer.ready)
+        tape.backward(g_rel=up["rel"], g_importance=up["importance"], on_ready=self._ready(0))
         self.reducer.finish()
         guard = head._loss.assign_status if self.device_targets else None
         self.apply_gradients(guard=guard)

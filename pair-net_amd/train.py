@@ -23,10 +23,10 @@ Per step: `head.forward` (the inference kernels; hipGraphs if on) -> `head.loss(
 loss.hip; the two Hungarian assignments on the host as the reference) -> `RelationTailGrad`
 (/ `HeadGrad` / `PixelDecoderGrad` / `BackboneGrad` / `SwinBackboneGrad` / `SwinStagesGrad`) forward-with-tape + backward into one flat
 gradient buffer -> (world > 1) bucketed all-reduce
-overlapped with the backward pass (`dist.GradReducer`) -> global-norm clip coefficient on the
-device -> ONE AdamW launch over the flat parameter buffer that the head's weight dict aliases ->
-refresh of the derived weight packs the inference kernels read.  No host synchronisation inside a
-step apart from the reference's own (the Hungarian cost matrices).
+overlapped with the backward pass (`dist.GradReducer`) -> clip, ONE AdamW launch, refresh of the
+derived weight packs (`FlatTrainer`, flat_trainer.py: the flat buffers, their set-up and everything
+behind the backward pass are shared with the other two training steps).  No host synchronisation
+inside a step apart from the reference's own (the Hungarian cost matrices).
 
 `TailTrainer(head, device_targets=True)` removes that one too: the assignments and the target
 bookkeeping run on the device (`head.loss(..., device_targets=True)`, csrc/assign.hip) and `step()`
@@ -52,22 +52,18 @@ with the two dropouts per layer (csrc/dropout.hip: Philox4x32-10 keyed by `seed`
 and d loss / d rel are those of the dropped logits, and nothing else of the outputs changes -- and
 the backward pass re-draws the same masks from the same counter.  The inference path never drops.
 """
-from collections import OrderedDict
-
 import torch
 
 from . import hip
 from .dist import GradReducer
+from .flat_trainer import (MATRIX_LEARNER_REPACKED, FlatTrainer, refresh_encoder,
+                           refresh_key_positions, refresh_matrix_learner, refresh_q0,
+                           refresh_query_positions, refresh_r0, refresh_relation_cross_attention,
+                           refresh_resnet, refresh_self_attention, refresh_swin, step_lr)
 from .grad import (BackboneGrad, FfnDropout, HeadGrad, PixelDecoderGrad, RelationTailGrad,
                    SwinBackboneGrad, SwinStagesGrad)
 
 __all__ = ["TailTrainer", "step_lr", "segment_multipliers"]
-
-
-def step_lr(base_lr, epoch, steps=(5, 10), gamma=0.5):
-    """mmcv's StepLrUpdaterHook by epoch (`lr_config = dict(policy="step", gamma=0.5, step=[5, 10])`,
-    configs/mask2former/pairnet.py:370): the learning rate of 0-based `epoch`."""
-    return base_lr * gamma ** sum(1 for s in steps if epoch >= s)
 
 
 def segment_multipliers(names, frozen, lr_mult=None, decay_mult=None, norm_decay_mult=0.0,
@@ -90,7 +86,7 @@ def segment_multipliers(names, frozen, lr_mult=None, decay_mult=None, norm_decay
     return lrs, wds
 
 
-class TailTrainer:
+class TailTrainer(FlatTrainer):
     FROZEN_GROUPS = ("cls",)      # cls_embed / post_norm: no gradient in the reference's graph
 
     def __init__(self, head, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8,
@@ -106,7 +102,6 @@ class TailTrainer:
         every tensor but the head's norms, as before; {"backbone.": 0.0} is
         configs/deformable_detr/cross_swinb_vg.py:564).  A key hit decides alone (a rule not pinned
         to mmcv's, as for `lr_mult`)."""
-        self.head = head
         # `device_targets`: loss targets built on the device, a guarded update, no host wait in
         # `step()` (module docstring); default off: the host assignments, launch for launch
         self.device_targets = bool(device_targets)
@@ -120,7 +115,6 @@ class TailTrainer:
         # `frozen_stages` below the last stage trains every stage from there down
         # (`SwinStagesGrad`; DropPath then on every trainable block).
         from .swin import SwinTransformerHip
-        self.backbone = backbone
         self.swin = isinstance(backbone, SwinTransformerHip)
         self.drop_path = bool(drop_path) and self.swin
         self._gen = torch.Generator().manual_seed(int(seed))
@@ -136,93 +130,34 @@ class TailTrainer:
         import torch.distributed as dist
         ini = dist.is_available() and dist.is_initialized()      # (as GradReducer reads `group`)
         self.subseq = int(dist.get_rank(group)) if ini else 0
-        train_pixel_decoder = bool(train_pixel_decoder) or backbone is not None
-        self.train_pixel_decoder = bool(train_pixel_decoder)
+        self.train_pixel_decoder = bool(train_pixel_decoder) or backbone is not None
         self.train_decoder = bool(train_decoder) or self.train_pixel_decoder
-        train_decoder = self.train_decoder
         if lr_mult is None:
             lr_mult = {"transformer_decoder": 0.1, "pixel_decoder": 0.1,
                        "backbone.": 0.01 if self.swin else 0.1}
-        if head.w is None:
-            head._pack()
-        # plans captured so far bake the addresses of the weight tensors that are re-homed below
-        # into their hipGraphs: start from fresh plans (the arenas, shape-dependent only, stay)
-        from .plans import PlanCache
-        head._plans = PlanCache(head._plans.max_plans)
-        dev = self.dev = head.device
-        tape_cls = HeadGrad if train_decoder else RelationTailGrad
-        # ONE flat gradient buffer for every tape: [head tape | pixel decoder tape]
-        n_head = tape_cls.size_of(head)
-        n_pd = PixelDecoderGrad.size_of(head) if self.train_pixel_decoder else 0
-        if backbone is not None:
-            if backbone.device is None:
-                backbone.to(dev)
-            if backbone.w is None:
-                backbone._pack()
         self.swin_stages = self.swin and backbone.frozen_stages < len(backbone.depths) - 1
+        tape_cls = HeadGrad if self.train_decoder else RelationTailGrad
         bb_cls = (SwinStagesGrad if self.swin_stages else SwinBackboneGrad) if self.swin \
             else BackboneGrad
-        n_bb = bb_cls.size_of(backbone) if backbone is not None else 0
-        self.flat_grad = torch.zeros(n_head + n_pd + n_bb, device=dev, dtype=torch.float32)
-        self.tape = tape = tape_cls(head, flat=self.flat_grad, base=0)
-        self.pd_tape = PixelDecoderGrad(head, flat=self.flat_grad, base=n_head) \
-            if self.train_pixel_decoder else None
-        self.bb_tape = bb_cls(backbone, flat=self.flat_grad, base=n_head + n_pd) \
-            if backbone is not None else None
-        self.lr, self.wd, self.betas, self.eps, self.max_norm = lr, weight_decay, betas, eps, max_norm
-        # name -> (offset in the shared buffer, shape, numel); the class path (cls_embed /
-        # post_norm: no gradient in the reference's graph) stays in the layout with lr 0
-        self.layout = OrderedDict(tape.layout)
-        if self.pd_tape is not None:
-            for n, (o, shape, k) in self.pd_tape.layout.items():
-                self.layout[n] = (o + n_head, shape, k)
-        src = {n: head._params[n] for n in self.layout}          # where a parameter's value lives
-        if self.bb_tape is not None:
-            for n, (o, shape, k) in self.bb_tape.layout.items():
-                self.layout["backbone." + n] = (o + n_head + n_pd, shape, k)
-                src["backbone." + n] = backbone._params[n]
-        frozen = {n for g, names in tape.param_groups(head) if g in self.FROZEN_GROUPS for n in names}
+        segments = [("tape", "", tape_cls, head)]
+        if self.train_pixel_decoder:
+            segments.append(("pd_tape", "", PixelDecoderGrad, head))
+        if backbone is not None:
+            segments.append(("bb_tape", "backbone.", bb_cls, backbone))
+        # the class path (cls_embed / post_norm: no gradient in the reference's graph) stays in
+        # the layout with lr 0
+        frozen = {n for g, names in tape_cls.param_groups(head) if g in self.FROZEN_GROUPS
+                  for n in names}
         if self.swin_stages:      # norm0: the loss does not reach C2 -- no gradient, no decay
             frozen |= {"backbone." + n for g, names in bb_cls.param_groups(backbone)
                        if g in bb_cls.NO_GRAD_GROUPS for n in names}
-        self.n = n_head + n_pd + n_bb
-        self.names = [n for n in self.layout if n not in frozen]
-        self._frozen = frozen
-        # ---- flat parameters; the head's device weights become views of them ----
-        self.flat_p = torch.zeros(self.n, device=dev, dtype=torch.float32)
-        self.flat_m = torch.zeros_like(self.flat_p)
-        self.flat_v = torch.zeros_like(self.flat_p)
-        w = head.w
-        self.params = OrderedDict()
-        ml = "update_importance.conv_layers."
-        self._repacked = {ml + "1.0.weight", ml + "2.0.weight"}   # w[...] holds another layout
-        for n in self.layout:
-            o, shape, k = self.layout[n]
-            view = self.flat_p[o:o + k].view(shape)
-            view.copy_(src[n].to(dev))
-            if n in frozen:
-                continue
-            self.params[n] = view
-            if n.startswith("backbone."):
-                continue          # the backbone's packed weights are all derived (BatchNorm folded)
-            if n not in self._repacked:
-                # same bytes as the reference layout (ConvTiny's first layer: [64,1,7,7] == [64,49],
-                # the 1x1 input convolutions: [256,C,1,1] == [256,C])
-                w[n] = view.view(w[n].shape)
-        # ---- per-segment multipliers (mmcv paramwise_cfg) ----
-        offs = [self.layout[n][0] for n in self.layout]
-        lrs, wds = segment_multipliers(self.layout, frozen, lr_mult, decay_mult, norm_decay_mult,
-                                       swin=self.swin)
-        offs.append(self.n)
-        self.seg_off = torch.tensor(offs, dtype=torch.int64, device=dev)
-        self.seg_lr = torch.tensor(lrs, dtype=torch.float32, device=dev)
-        self.seg_wd = torch.tensor(wds, dtype=torch.float32, device=dev)
-        self.clip = torch.zeros(2, device=dev, dtype=torch.float32)     # [grad norm, coefficient]
-        self._scratch = torch.zeros(256, device=dev, dtype=torch.float64)
+        super().__init__(
+            head, segments,
+            lambda names, frozen: segment_multipliers(names, frozen, lr_mult, decay_mult,
+                                                      norm_decay_mult, swin=self.swin),
+            backbone=backbone, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps,
+            max_norm=max_norm, frozen=frozen, repacked=MATRIX_LEARNER_REPACKED)
         self.reducer = GradReducer(self.flat_grad, group=group, bucket_bytes=bucket_bytes)
-        self.steps = 0
-        self._w_dicts = (head.w, backbone.w if backbone is not None else None)
-        self._refresh_derived()
 
     # ------------------------------------------------------------------
     @staticmethod
@@ -251,96 +186,23 @@ class TailTrainer:
                           self.steps if step is None else step)
 
     def _refresh_derived(self):
-        """The weight packs the INFERENCE kernels read that are functions of trained parameters,
-        rewritten in place (captured hipGraphs keep their pointers)."""
+        """The packs of what this trainer trains (flat_trainer.py); both decoders are
+        cross-attention first: their self-attention is `attentions.1`."""
         head, w, p = self.head, self.head.w, self.params
-        decs = [("relation_decoder", head.num_rel_layers)]
+        refresh_self_attention(head, w, p, "relation_decoder", head.num_rel_layers, 1)
+        refresh_relation_cross_attention(head, w, p)
+        refresh_matrix_learner(head, w, p)
+        refresh_r0(head, w, p)
         if self.train_decoder:
-            decs.append(("transformer_decoder", head.num_dec_layers))
-        for dec, nl in decs:                       # self-attention as one [V | Q | K] projection
-            for i in range(nl):
-                a = "%s.layers.%d.attentions.1.attn." % (dec, i)
-                W, b = p[a + "in_proj_weight"], p[a + "in_proj_bias"]
-                w[a + "vqk.weight"][:256].copy_(W[512:])
-                w[a + "vqk.weight"][256:].copy_(W[:512])
-                w[a + "vqk.bias"][:256].copy_(b[512:])
-                w[a + "vqk.bias"][256:].copy_(b[:512])
-        for i in range(head.num_rel_layers):       # relation cross-attention keys / values: [V | K]
-            a = "relation_decoder.layers.%d.attentions.0.attn." % i
-            W, b = p[a + "in_proj_weight"], p[a + "in_proj_bias"]
-            w[a + "vk.weight"][:256].copy_(W[512:])
-            w[a + "vk.weight"][256:].copy_(W[256:512])
-            w[a + "vk.bias"][:256].copy_(b[512:])
-            w[a + "vk.bias"][256:].copy_(b[256:512])
-        ml = "update_importance.conv_layers."
-        w[ml + "1.0.weight"].copy_(p[ml + "1.0.weight"].permute(0, 2, 3, 1).reshape(64, -1))
-        w[ml + "2.0.weight"].copy_(p[ml + "2.0.weight"].reshape(64, 49).t())
-        for c in head._consts.values():           # rel_query_feat repeated over the batch
-            if "r0" in c:
-                B = c["r0"].shape[0] // p["rel_query_feat.weight"].shape[0]
-                c["r0"].view(B, -1, 256).copy_(p["rel_query_feat.weight"].unsqueeze(0).expand(B, -1, -1))
-        if self.train_decoder:
-            from types import SimpleNamespace
-            for c in head._consts.values():       # the initial queries and their mask embedding
-                if "q0" not in c:
-                    continue
-                BQ = c["q0"].shape[0]
-                B = BQ // p["query_feat.weight"].shape[0]
-                c["q0"].view(B, -1, 256).copy_(p["query_feat.weight"].unsqueeze(0).expand(B, -1, -1))
-                if c.get("me0") is not None:
-                    tmp = SimpleNamespace(B=B, cls=None, MP=None,
-                                          **{n: torch.empty(BQ, 256, device=self.dev)
-                                             for n in ("qn", "m1", "m2", "me")})
-                    head._head_embed(c["q0"], tmp, False, False)
-                    c["me0"].copy_(tmp.me)
-            for shapes, ent in head._pe.items():  # key position tables carry level_embed
-                for l, (h, wd) in enumerate(shapes):
-                    hip.sine_pe(ent[1][l], p["level_embed.weight"][l], h, wd)
+            refresh_self_attention(head, w, p, "transformer_decoder", head.num_dec_layers, 1)
+            refresh_q0(head, w, p)
+            refresh_key_positions(head, w, p)
         if self.train_pixel_decoder:
-            pd = "pixel_decoder."
-            for i in range(head.num_enc_layers):
-                q, a = pd + "encoder.layers.%d." % i, pd + "encoder.layers.%d.attentions.0." % i
-                # one [value_proj | sampling_offsets | attention_weights] projection per layer
-                o = 0
-                for n in ("value_proj", "sampling_offsets", "attention_weights"):
-                    r = p[a + n + ".weight"].shape[0]
-                    w[a + "voa.weight"][o:o + r].copy_(p[a + n + ".weight"])
-                    w[a + "voa.bias"][o:o + r].copy_(p[a + n + ".bias"])
-                    o += r
-                for k in (a + "voa.weight", a + "output_proj.weight", q + "ffns.0.layers.0.0.weight",
-                          q + "ffns.0.layers.1.weight"):
-                    hip.s3_split(w[k], w[k + ".s3"])          # the bf16-pipe GEMMs' operands
-            for shapes, ent in head._pe.items():  # query position tables carry level_encoding
-                o = 0
-                for l, (h, wd) in enumerate(shapes):
-                    hip.sine_pe(ent[0][o:o + h * wd], p[pd + "level_encoding.weight"][l], h, wd)
-                    o += h * wd
-                ent[3].copy_(hip.pos8(ent[0]))
+            refresh_encoder(head, w, p)
+            refresh_query_positions(head, w, p)
         if self.bb_tape is not None:
-            self._refresh_swin() if self.swin else self._refresh_backbone()
-
-    def _refresh_swin(self):
-        """Rewrite the Swin backbone's packed weights of the trained stages in place, as
-        `SwinTransformerHip._pack` derives them: the bias tables transposed to
-        [heads][(2ws-1)^2], the block GEMMs' bf16-plane splits, the patch-merging norm and
-        reduction weight in neighbour-major column order, the patch-embedding weight in the first
-        48 of its 64 columns."""
-        w, p = self.backbone.w, self.params
-        for n in self.bb_tape.layout:
-            v = p.get("backbone." + n)
-            if v is None:                          # (norm0 without a gradient: never moves)
-                continue
-            if n.endswith("relative_position_bias_table"):
-                v = v.t()
-            elif ".downsample." in n:              # nn.Unfold order c*4 + q -> q*C + c
-                c = v.shape[-1] // 4
-                v = v.reshape(*v.shape[:-1], c, 4).transpose(-1, -2).reshape(v.shape)
-            if n == "patch_embed.projection.weight":
-                w[n][:, :48].copy_(v.reshape(v.shape[0], 48))
-            else:
-                w[n].copy_(v)
-            if n + ".s3" in w:
-                hip.s3_split(w[n], w[n + ".s3"])
+            (refresh_swin if self.swin else refresh_resnet)(self.backbone, self.backbone.w, p,
+                                                            self.bb_tape)
 
     def _drop_path_keep(self, B):
         """mmdet DropPath's per-image scale factors [blocks, 2 branches, B] of the trained stage:
@@ -357,42 +219,6 @@ class TailTrainer:
         return keep.pin_memory().to(self.dev, non_blocking=True) if torch.cuda.is_available() \
             else keep
 
-    def _refresh_backbone(self):
-        """Re-fold BatchNorm into the trained convolutions and rewrite the backbone's packed
-        weights (channel-last rows, Winograd transforms, bf16-plane splits) in place."""
-        bb, p = self.backbone, self.params
-        w = bb.w
-        for n, sc in self.bb_tape.bn_scale64.items():
-            conv = n[:-len(".weight")]
-            # W' = W gamma / sqrt(var + eps), formed in double and rounded once like `_fold`
-            cw = (p["backbone." + n].double() * sc.view(-1, 1, 1, 1)).float()
-            co = cw.shape[0]
-            w[conv + ".w"].copy_(cw.permute(0, 2, 3, 1).reshape(co, -1))
-            if conv + ".wino" in w:
-                w[conv + ".wino"].copy_(hip.winograd_weights(cw.contiguous()))
-                w[conv + ".wino4"].copy_(hip.winograd43_weights(cw.contiguous()))
-            if conv + ".w.s3" in w:
-                hip.s3_split(w[conv + ".w"], w[conv + ".w.s3"])
-
-    def set_epoch(self, epoch, steps=(5, 10), gamma=0.5):
-        """The reference's learning-rate schedule (step policy by epoch): sets `self.lr`."""
-        if not hasattr(self, "base_lr"):
-            self.base_lr = self.lr
-        self.lr = step_lr(self.base_lr, epoch, steps, gamma)
-        return self.lr
-
-    def write_back(self):
-        """Copy the trained values into the head's (and the backbone's) state dict (checkpoints,
-        `state_dict()`)."""
-        head = self.head
-        for n, v in self.params.items():
-            dst = self.backbone._params[n[len("backbone."):]] if n.startswith("backbone.") \
-                else head._params[n]
-            dst.copy_(v.to(dst.device))
-        head._packed_version = head._weights_version()     # the packed device weights ARE these values
-        if self.backbone is not None and hasattr(self.backbone, "_weights_version"):
-            self.backbone._packed_version = self.backbone._weights_version()
-
     # ------------------------------------------------------------------
     @torch.no_grad()
     @hip.on_device
@@ -403,12 +229,7 @@ class TailTrainer:
         matrices were refused and the update was skipped).  `feats`: the four backbone feature
         maps -- or, for a trainer built with `backbone=`, the image tensor."""
         head, tape = self.head, self.tape
-        if head.w is not self._w_dicts[0] or (self.backbone is not None
-                                              and self.backbone.w is not self._w_dicts[1]):
-            # load_state_dict / an in-place parameter update made the module re-pack its device
-            # weights: the flat buffers of this trainer no longer back them
-            raise RuntimeError("the head (or backbone) re-packed its weights since this TailTrainer "
-                               "was built (load_state_dict, parameter update, .to()): build a new one")
+        self._check_not_repacked()
         if self.swin_stages:                   # the tape runs the whole backbone from the image
             keep = self._drop_path_keep(feats.shape[0]) if self.drop_path else None
             feats = [c.permute(0, 3, 1, 2) for c in self.bb_tape.forward(feats, keep)]
@@ -445,26 +266,21 @@ class TailTrainer:
         if self.pd_tape is not None:
             self.pd_tape.forward(feats)
         self.reducer.start()
-        nh = tape.flat_numel
-        back = tape.backward(g_rel=up["rel"], g_importance=up["importance"],
-                             on_ready=lambda e: self.reducer.ready(min(e, nh)))
+        back = tape.backward(g_rel=up["rel"], g_importance=up["importance"], on_ready=self._ready(0))
         if self.pd_tape is not None:           # back[0]: d memory tokens (HeadGrad)
-            npd = self.pd_tape.flat_numel
-            dfeats, _ = self.pd_tape.backward(back[0], on_ready=lambda e: self.reducer.ready(nh + e))
+            dfeats, _ = self.pd_tape.backward(back[0], on_ready=self._ready(1))
             if self.swin_stages:               # dfeats: d C5, d C4, d C3
-                self.bb_tape.backward(dfeats[2], dfeats[1], dfeats[0],
-                                      on_ready=lambda e: self.reducer.ready(nh + npd + e))
+                self.bb_tape.backward(dfeats[2], dfeats[1], dfeats[0], on_ready=self._ready(2))
             elif self.bb_tape is not None and self.swin:   # d C5; C2-C4 come from frozen stages
-                self.bb_tape.backward(dfeats[0], on_ready=lambda e: self.reducer.ready(nh + npd + e))
+                self.bb_tape.backward(dfeats[0], on_ready=self._ready(2))
             elif self.bb_tape is not None:     # dfeats: d C5, d C4, d C3
                 self.bb_tape.forward(feats[0])
-                self.bb_tape.backward(dfeats[2], dfeats[1], dfeats[0],
-                                      on_ready=lambda e: self.reducer.ready(nh + npd + e))
+                self.bb_tape.backward(dfeats[2], dfeats[1], dfeats[0], on_ready=self._ready(2))
         self.reducer.finish()
         # (a call whose sizes exceed the device solver's took the host path, which raises itself)
         guard = head._loss.assign_status if self.device_targets and head._loss.last_on_device \
             else None
-        if guard is None:
+        if guard is None:          # (callers that replace `apply_gradients` take no argument)
             self.apply_gradients()
         else:
             self.apply_gradients(guard=guard)
@@ -474,18 +290,3 @@ class TailTrainer:
             out["assign_status"] = guard[0] if guard is not None else \
                 torch.zeros((), dtype=torch.int32, device=self.dev)
         return out
-
-    @torch.no_grad()
-    @hip.on_device
-    def apply_gradients(self, guard=None):
-        """Clip (global L2 norm over the trainable gradients) + AdamW on `tape.flat_grad`.
-        `guard`: a device int32 word; non-zero skips the update on the device (`steps` advances
-        all the same)."""
-        g = self.flat_grad
-        pre = self.reducer.scale
-        hip.grad_norm_clip(g, self.clip, self._scratch, pre=pre, max_norm=self.max_norm)
-        self.steps += 1
-        hip.adamw(self.flat_p, g, self.flat_m, self.flat_v, self.seg_off, self.seg_lr, self.seg_wd,
-                  self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.steps,
-                  clip=self.clip, pre=pre, guard=guard)
-        self._refresh_derived()
