@@ -359,12 +359,39 @@ int pn_msda_loc_f32(const float* value, int64_t ld_value, const int64_t* spatial
  *   grad_attn_weight    [B][Nq][8][L][4]     written
  * Arithmetic of mmcv's ms_deform_attn_col2im_bilinear (locations outside (-1, H) x (-1, W)
  * contribute nothing); grad_value's summation order is not deterministic (nor is mmcv's), the
- * other two outputs are. */
+ * other two outputs are.  pn_msda_bwd_det_f32 below is the reproducible form. */
 int pn_msda_bwd_f32(const float* value, int64_t ld_value, const int64_t* spatial_shapes,
                     const int64_t* level_start_index, const float* sampling_locations,
                     const float* attention_weights, const float* grad_output, float* grad_value,
                     float* grad_sampling_loc, float* grad_attn_weight, int B, int N, int Nq, int L,
                     void* stream);
+
+/* The same backward with a bitwise reproducible grad_value: no floating-point atomics (mmcv's
+ * mmcv/ops/csrc/pytorch/cuda/ms_deform_attn_cuda.cu, `ms_deformable_col2im`, adds them with
+ * atomicAdd; csrc/msda_grad.hip builds an inverted index per destination instead).  Operands of
+ * pn_msda_bwd_f32 plus a caller-owned scratch of at least pn_msda_bwd_det_scratch_bytes(B, N, Nq,
+ * L) bytes, 16-byte aligned, which may arrive dirty.  Definition of the result: for every
+ * destination (b, token, head) the contributions are the in-map bilinear taps of all (q, l, p)
+ * that land on the token (pn_msda_bwd_f32's in-map tests and clamping), taps numbered t = 0..3 in
+ * the order (ya,xa), (ya,xb), (yb,xa), (yb,xb); a contribution's id is ((q*L + l)*4 + p)*4 + t and
+ * its coefficient coef = w_t * a (bilinear weight times attention weight, one fp32 rounding).
+ * Per channel c: acc = 0, then over the destination's contributions in ASCENDING id
+ *   acc = fmaf(coef, grad_output[b][q][head*32 + c], acc)
+ * and finally grad_value[b][token][head][c] += acc, one read-modify-write by its single owner
+ * (so the entry accumulates into a caller-zeroed buffer exactly as mmcv's does); a destination
+ * without a contribution is not written.  grad_sampling_loc / grad_attn_weight are overwritten
+ * and are bit for bit pn_msda_bwd_f32's.  All launches go on `stream`; nothing is allocated,
+ * uploaded or waited for (graph-capturable).  PN_BAD_ARG: whatever pn_msda_bwd_f32 refuses, a
+ * NULL, short or misaligned scratch, Nq*L*16, B*Nq*8*L*16 or B*8*N above 2^31 - 1.
+ * pn_msda_bwd_det_scratch_bytes returns 0 for such arguments.  Entries added at ABI 34 (adding
+ * entries is compatible). */
+int64_t pn_msda_bwd_det_scratch_bytes(int B, int N, int Nq, int L);
+int pn_msda_bwd_det_f32(const float* value, int64_t ld_value, const int64_t* spatial_shapes,
+                        const int64_t* level_start_index, const float* sampling_locations,
+                        const float* attention_weights, const float* grad_output,
+                        float* grad_value, float* grad_sampling_loc, float* grad_attn_weight,
+                        void* scratch, int64_t scratch_bytes, int B, int N, int Nq, int L,
+                        void* stream);
 
 /* Diagnostic (bench.py's `roofline_deformable_sampling.gather_peak`): the bare access pattern of
  * the sampling kernels above -- 8 lanes x 16 B per random 128-byte line, 12 independent lines per

@@ -236,12 +236,14 @@ class CrossHeadBaseline(CrossHead2):
         self._seg_tape.forward_from_plan(pl)
         return self._seg_tape.backward(grads, counts=self._seg_loss.last["counts"])
 
-    def segmenter_backward(self, grads, feats, pl=None, need_dc2=False):
+    def segmenter_backward(self, grads, feats, pl=None, need_dc2=False, deterministic=False):
         """`seg_backward(grads, pl)`, then its (dmem, dMF) on through the pixel decoder, FPN branch
         included (`SegPixelDecoderGrad`, whose forward runs on `feats`, the backbone pyramid the
         plan's forward saw) -> (dfeats, {reference parameter name: gradient}): dfeats = [d C5, d C4,
         d C3, d C2 or None without `need_dc2`], the dict is the union of the trunk's and the pixel
-        decoder's.  The tape is built on first use and kept.
+        decoder's.  The tape is built on first use and kept.  `deterministic`: the tape's
+        deformable-attention backward without float atomics (`PixelDecoderGrad.deterministic`):
+        bitwise reproducible results.
 
         Known limitation: as in `TailTrainer`, the pixel decoder's tape runs its own exact-fp32
         forward while the plan ran the encoder in `gemm_arithmetic`, so the two halves are
@@ -251,6 +253,7 @@ class CrossHeadBaseline(CrossHead2):
         if self._segpd_tape is None:
             from .seg_grad import SegPixelDecoderGrad
             self._segpd_tape = SegPixelDecoderGrad(self)
+        self._segpd_tape.deterministic = bool(deterministic)
         self._segpd_tape.forward(feats)
         dfeats, g_pd = self._segpd_tape.backward(dmem, dMF, need_dc2=need_dc2)
         assert not set(g_trunk) & set(g_pd)
@@ -281,16 +284,17 @@ class CrossHeadBaseline(CrossHead2):
         self._head_tape.forward_from_plan(pl, dropout=dropout)
         return self._head_tape.backward(grads, counts=self._seg_loss.last["counts"])
 
-    def full_backward(self, grads, feats, pl=None, need_dc2=False):
+    def full_backward(self, grads, feats, pl=None, need_dc2=False, deterministic=False):
         """`head_backward(grads, pl)`, then its (dmem, dMF) on through the pixel decoder, FPN branch
         included, as `segmenter_backward` chains its two parts -> (dfeats, {reference parameter
         name: gradient}) with dfeats = [d C5, d C4, d C3, d C2 or None without `need_dc2`] (what
         `BackboneGrad` takes).  The same known limitation as `segmenter_backward`: the pixel
-        decoder's tape runs its own exact-fp32 forward."""
+        decoder's tape runs its own exact-fp32 forward.  `deterministic`: as in `segmenter_backward`."""
         dmem, dMF, g_head = self.head_backward(grads, pl)
         if self._segpd_tape is None:
             from .seg_grad import SegPixelDecoderGrad
             self._segpd_tape = SegPixelDecoderGrad(self)
+        self._segpd_tape.deterministic = bool(deterministic)
         self._segpd_tape.forward(feats)
         dfeats, g_pd = self._segpd_tape.backward(dmem, dMF, need_dc2=need_dc2)
         assert not set(g_head) & set(g_pd)

@@ -68,12 +68,14 @@ class BaselineTrainer(FlatTrainer):
 
     def __init__(self, head, backbone=None, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999),
                  eps=1e-8, max_norm=0.1, lr_mult=None, decay_mult=None, norm_decay_mult=0.0, seed=0,
-                 masked_keysplit_min_keys="default"):
+                 masked_keysplit_min_keys="default", deterministic=False):
         """`lr_mult` / `decay_mult`: {substring of a parameter name: multiplier} (mmcv's
         `paramwise_cfg.custom_keys`; default: the four keys of the module docstring at 0.1); a
         backbone's parameters appear as "backbone.<name>".  `masked_keysplit_min_keys`: the head
         tape's switch (None: `pn_mha_bwd_f32` for all nine masked cross-attentions); the default
-        is the measured `MASKED_KEYSPLIT_MIN_KEYS`."""
+        is the measured `MASKED_KEYSPLIT_MIN_KEYS`.  `deterministic`: the pixel-decoder tape's
+        deformable-attention backward without float atomics (`PixelDecoderGrad.deterministic`,
+        `pn_msda_bwd_det_f32`): the whole step is then bitwise reproducible."""
         from .swin import SwinTransformerHip
         if not hasattr(head, "_relation_stage") or not hasattr(head, "full_losses"):
             raise NotImplementedError("BaselineTrainer trains a CrossHeadBaseline (%s: TailTrainer)"
@@ -100,6 +102,8 @@ class BaselineTrainer(FlatTrainer):
         self.tape.masked_keysplit_min_keys = self.MASKED_KEYSPLIT_MIN_KEYS \
             if isinstance(masked_keysplit_min_keys, str) and masked_keysplit_min_keys == "default" \
             else masked_keysplit_min_keys
+        self.deterministic = bool(deterministic)
+        self.pd_tape.deterministic = self.deterministic
         self._guard = torch.zeros(1, device=self.dev, dtype=torch.int32)
 
     # ------------------------------------------------------------------

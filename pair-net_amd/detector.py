@@ -609,8 +609,9 @@ class PSGTr:
         regimes; `dropout=True` trains with the relation decoder's configured FFN dropout,
         `seed=` its masks; `device_targets=True` builds the loss targets on the device -- Hungarian
         assignments in HIP, a guarded AdamW launch -- so that `TailTrainer.step` holds no host wait
-        and `train_step` returns `assign_status` beside the losses; nothing of it lives here, the
-        keywords pass through)."""
+        and `train_step` returns `assign_status` beside the losses; `deterministic=True` runs the
+        pixel decoder's deformable-attention backward without float atomics, a bitwise reproducible
+        step; nothing of it lives here, the keywords pass through)."""
         from .backbone import ResNet50Hip
         from .train import TailTrainer
         if type(self.bbox_head) is not CrossHead2:
@@ -677,7 +678,8 @@ class PSGTr:
         (baseline_train.py).  `train_backbone`: None (default) / True trains a ResNet
         backbone's stages 2-4 (`step` then takes the image), False leaves the backbone frozen
         (`step` takes its features); True with a Swin backbone raises.  Other keywords go to
-        `BaselineTrainer` (lr, lr_mult, decay_mult, seed, masked_keysplit_min_keys).  `trainer()`,
+        `BaselineTrainer` (lr, lr_mult, decay_mult, seed, masked_keysplit_min_keys,
+        `deterministic=True` for a bitwise reproducible step without float atomics).  `trainer()`,
         `train_step()` and `val_losses()` keep refusing this head."""
         from .backbone import ResNet50Hip
         from .baseline_train import BaselineTrainer

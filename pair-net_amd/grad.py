@@ -838,9 +838,17 @@ class PixelDecoderGrad(RelationTailGrad):
     differentiated in mmcv's own operand set (`pn_msda_loc_f32` forward, `pn_msda_bwd_f32`: atomics
     on grad_value, like mmcv's), its operands come from `pn_token_sampling_f32` and go back through
     `pn_msda_offaw_bwd_f32`; the forward runs on the exact-fp32 MFMA kernels whatever
-    `head.gemm_arithmetic` says."""
+    `head.gemm_arithmetic` says.
+
+    `deterministic` (class attribute, False): set it on a tape and `backward` runs
+    `pn_msda_bwd_det_f32` (csrc/msda_grad.hip) instead -- grad_value summed per destination in a
+    fixed order, no float atomics -- and every result of the walk is bitwise reproducible.  Its
+    six layers share ONE scratch tensor (`msda_scratch`), allocated at the first such backward and
+    kept across steps; a tape that never runs deterministically never allocates it."""
 
     PD = "pixel_decoder."
+    deterministic = False
+    msda_scratch = None
 
     @staticmethod
     def param_groups(head):
@@ -970,8 +978,15 @@ class PixelDecoderGrad(RelationTailGrad):
             dS = self._lin_bwd(dxn, s["S"], w[a + "output_proj.weight"], grads,
                                a + "output_proj.weight", a + "output_proj.bias")
             gval, gloc, gaw = zeros(M, 256), E(M * 8 * 3 * 4 * 2), E(M * 8 * 3 * 4)
-            hip.msda_bwd(s["value"], 256, t["shapes_dev"], t["lsi_dev"], s["loc"], s["aw"], dS, gval,
-                         gloc, gaw, B, SN, SN, 3)
+            if self.deterministic:
+                need = hip.msda_bwd_det_scratch_bytes(B, SN, SN, 3)
+                if self.msda_scratch is None or self.msda_scratch.numel() < need:
+                    self.msda_scratch = torch.empty(need, dtype=torch.uint8, device=self.dev)
+                hip.msda_bwd_det(s["value"], 256, t["shapes_dev"], t["lsi_dev"], s["loc"], s["aw"],
+                                 dS, gval, gloc, gaw, B, SN, SN, 3, scratch=self.msda_scratch)
+            else:
+                hip.msda_bwd(s["value"], 256, t["shapes_dev"], t["lsi_dev"], s["loc"], s["aw"], dS,
+                             gval, gloc, gaw, B, SN, SN, 3)
             self._acc(dxn, self._lin_bwd(gval, s["x_in"], w[a + "value_proj.weight"], grads,
                                          a + "value_proj.weight", a + "value_proj.bias"))
             d_offaw = E(M, 288)

@@ -155,6 +155,8 @@ _SIGS = {
     "pn_loss_targets": (C.c_int, [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32] + [_vp] * 5),
     "pn_msda_loc_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pn_msda_bwd_f32": (C.c_int, [_vp, _i64] + [_vp] * 8 + [_i32, _i32, _i32, _i32, _vp]),
+    "pn_msda_bwd_det_scratch_bytes": (C.c_int64, [_i32, _i32, _i32, _i32]),
+    "pn_msda_bwd_det_f32": (C.c_int, [_vp, _i64] + [_vp] * 9 + [_i64, _i32, _i32, _i32, _i32, _vp]),
     "pn_gather_probe_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "pn_sine_pe_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "pn_sine_pe_offset_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _vp]),
@@ -861,6 +863,26 @@ def msda_bwd(value, ld_value, spatial_shapes, level_start_index, loc, aw, grad_o
                                  _ptr(level_start_index, torch.int64), _ptr(loc), _ptr(aw),
                                  _ptr(grad_out), _ptr(grad_value), _ptr(grad_loc), _ptr(grad_aw),
                                  B, N, Nq, L, _stream()), "pn_msda_bwd_f32")
+
+
+def msda_bwd_det_scratch_bytes(B, N, Nq, L):
+    """Bytes of scratch pn_msda_bwd_det_f32 needs at these sizes (0: sizes it refuses)."""
+    return int(lib().pn_msda_bwd_det_scratch_bytes(B, N, Nq, L))
+
+
+def msda_bwd_det(value, ld_value, spatial_shapes, level_start_index, loc, aw, grad_out, grad_value,
+                 grad_loc, grad_aw, B, N, Nq, L, scratch=None):
+    """msda_bwd with a bitwise reproducible grad_value (no float atomics; csrc/msda_grad.hip).
+    `scratch`: a torch.uint8 device tensor of at least msda_bwd_det_scratch_bytes(B, N, Nq, L)
+    bytes, contents arbitrary; None allocates one."""
+    if scratch is None:
+        scratch = torch.empty(max(msda_bwd_det_scratch_bytes(B, N, Nq, L), 16), dtype=torch.uint8,
+                              device=value.device)
+    _check(lib().pn_msda_bwd_det_f32(_ptr(value), ld_value, _ptr(spatial_shapes, torch.int64),
+                                     _ptr(level_start_index, torch.int64), _ptr(loc), _ptr(aw),
+                                     _ptr(grad_out), _ptr(grad_value), _ptr(grad_loc),
+                                     _ptr(grad_aw), _ptr(scratch, torch.uint8), scratch.numel(),
+                                     B, N, Nq, L, _stream()), "pn_msda_bwd_det_f32")
 
 
 def gather_probe(lines, idx, out, workgroups, line_mask):

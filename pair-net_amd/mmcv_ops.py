@@ -5,7 +5,9 @@
 `MultiScaleDeformableAttnFunction.forward`; configured for Pair-Net at
 configs/mask2former/pairnet.py:43-54) and runs the gfx950 kernel behind
 `pn_msda_loc_f32` (csrc/msda.hip); `ms_deform_attn_backward` has the argument list of
-`ext_module.ms_deform_attn_backward` and runs `pn_msda_bwd_f32`;
+`ext_module.ms_deform_attn_backward` and runs `pn_msda_bwd_f32` -- or, with `deterministic=True`
+or under `torch.use_deterministic_algorithms(True)`, `pn_msda_bwd_det_f32` (csrc/msda_grad.hip),
+whose `grad_value` is summed without floating-point atomics and is bitwise reproducible;
 `MultiScaleDeformableAttnFunction` is mmcv's autograd function of the same name over the two
 (what `MultiScaleDeformableAttention.forward` calls when `value.is_cuda`).  INTEGRATION.md
 shows how a maintainer points mmcv's module at them.  No CPU path.
@@ -55,13 +57,17 @@ def _check_shapes(value, sampling_locations):
 @torch.no_grad()
 def ms_deform_attn_backward(value, value_spatial_shapes, value_level_start_index,
                             sampling_locations, attention_weights, grad_output, grad_value,
-                            grad_sampling_loc, grad_attn_weight, im2col_step=64):
+                            grad_sampling_loc, grad_attn_weight, im2col_step=64,
+                            deterministic=None):
     """mmcv's `ext_module.ms_deform_attn_backward`: the three gradient tensors are the caller's
     (mmcv allocates them with `torch.zeros_like`) and are filled in place -- `grad_value`
     (bs, num_keys, num_heads, dims) is ACCUMULATED into (atomics, like mmcv's col2im), so it
     must arrive zeroed; `grad_sampling_loc` and `grad_attn_weight` (the shapes of
     `sampling_locations` / `attention_weights`) are overwritten.  `im2col_step` is accepted and
-    ignored.  Returns None."""
+    ignored.  `deterministic`: True sums `grad_value` per destination in a fixed order instead
+    (`pn_msda_bwd_det_f32`: no float atomics, bitwise reproducible, still accumulated into the
+    caller's buffer; its scratch is allocated per call), False keeps the atomics, None (default)
+    follows `torch.are_deterministic_algorithms_enabled()`.  Returns None."""
     bs, n, nq, levels = _check_shapes(value, sampling_locations)
     for t, like in ((grad_value, value), (grad_sampling_loc, sampling_locations),
                     (grad_attn_weight, attention_weights)):
@@ -69,18 +75,22 @@ def ms_deform_attn_backward(value, value_spatial_shapes, value_level_start_index
                 or t.device != value.device:
             raise RuntimeError("gradient buffers: contiguous fp32 device tensors shaped like "
                                "value / sampling_locations / attention_weights")
+    if deterministic is None:
+        deterministic = torch.are_deterministic_algorithms_enabled()
     with torch.cuda.device(value.device):
-        hip.msda_bwd(value.contiguous(), 256, value_spatial_shapes.contiguous(),
-                     value_level_start_index.contiguous(), sampling_locations.contiguous(),
-                     attention_weights.contiguous(), grad_output.contiguous(), grad_value,
-                     grad_sampling_loc, grad_attn_weight, bs, n, nq, levels)
+        bwd = hip.msda_bwd_det if deterministic else hip.msda_bwd
+        bwd(value.contiguous(), 256, value_spatial_shapes.contiguous(),
+            value_level_start_index.contiguous(), sampling_locations.contiguous(),
+            attention_weights.contiguous(), grad_output.contiguous(), grad_value,
+            grad_sampling_loc, grad_attn_weight, bs, n, nq, levels)
 
 
 class MultiScaleDeformableAttnFunction(torch.autograd.Function):
     """mmcv.ops.multi_scale_deform_attn.MultiScaleDeformableAttnFunction on the gfx950 kernels:
     `apply(value, value_spatial_shapes, value_level_start_index, sampling_locations,
     attention_weights, im2col_step)` -> (bs, num_queries, embed_dims), differentiable in
-    value, sampling_locations and attention_weights."""
+    value, sampling_locations and attention_weights.  The backward follows torch's own switch:
+    under `torch.use_deterministic_algorithms(True)` it is bitwise reproducible."""
 
     @staticmethod
     def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations,

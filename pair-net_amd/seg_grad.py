@@ -552,7 +552,9 @@ class SegPixelDecoderGrad(PixelDecoderGrad):
     the parent -- are bitwise reproducible.  The parent's walk is not, from the first
     `pn_msda_bwd_f32` on: that kernel adds grad_value with float atomics, like mmcv's
     (csrc/msda.hip), so everything behind layer 5's `value_proj` varies in its last bits from
-    call to call, as `PixelDecoderGrad.backward`'s results always have."""
+    call to call, as `PixelDecoderGrad.backward`'s results always have -- unless the tape's
+    `deterministic` attribute (inherited from the parent) is set: then the walk runs
+    `pn_msda_bwd_det_f32` and all of it is bitwise reproducible."""
 
     BRANCH_GROUPS = [
         ("mask_feature", [PixelDecoderGrad.PD + "mask_feature." + n for n in ("weight", "bias")]),

@@ -93,7 +93,7 @@ class TailTrainer(FlatTrainer):
                  max_norm=0.1, norm_decay_mult=0.0, lr_mult=None, group=None,
                  bucket_bytes=32 << 20, train_decoder=False, train_pixel_decoder=False,
                  backbone=None, drop_path=False, seed=0, dropout=False, device_targets=False,
-                 decay_mult=None):
+                 decay_mult=None, deterministic=False):
         """`train_decoder`: also train the nine masked decoder layers, `query_feat`, `query_embed`
         and `level_embed` (`HeadGrad`; the reference's `transformer_decoder` group, lr_mult 0.1 by
         default here as in configs/mask2former/pairnet.py:358-363) -- everything of the head behind
@@ -101,7 +101,10 @@ class TailTrainer(FlatTrainer):
         `paramwise_cfg.custom_keys`).  `decay_mult`: the same for the weight decay (None: 1 for
         every tensor but the head's norms, as before; {"backbone.": 0.0} is
         configs/deformable_detr/cross_swinb_vg.py:564).  A key hit decides alone (a rule not pinned
-        to mmcv's, as for `lr_mult`)."""
+        to mmcv's, as for `lr_mult`).  `deterministic`: the pixel-decoder tape's deformable-
+        attention backward without float atomics (`PixelDecoderGrad.deterministic`,
+        `pn_msda_bwd_det_f32`): the whole step is then bitwise reproducible; without a
+        pixel-decoder tape the keyword changes nothing."""
         # `device_targets`: loss targets built on the device, a guarded update, no host wait in
         # `step()` (module docstring); default off: the host assignments, launch for launch
         self.device_targets = bool(device_targets)
@@ -157,6 +160,9 @@ class TailTrainer(FlatTrainer):
                                                       norm_decay_mult, swin=self.swin),
             backbone=backbone, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps,
             max_norm=max_norm, frozen=frozen, repacked=MATRIX_LEARNER_REPACKED)
+        self.deterministic = bool(deterministic)
+        if self.pd_tape is not None:
+            self.pd_tape.deterministic = self.deterministic
         self.reducer = GradReducer(self.flat_grad, group=group, bucket_bytes=bucket_bytes)
 
     # ------------------------------------------------------------------

@@ -8,7 +8,12 @@ steps `flat_p` / `flat_m` / `flat_v` / `clip` / every returned value; `infer` (t
 outputs on the same input: the derived packs were refreshed); after `write_back()` the head's
 (and the backbone's) `state_dict()`.
 
-    python tools/trainer_digest.py [--out FILE] [--only tail,baseline_image]
+    python tools/trainer_digest.py [--out FILE] [--only tail,baseline_image] [--deterministic]
+
+`--deterministic` passes `deterministic=True` to the configurations with a pixel-decoder tape
+(PD_TAPE below): the deformable-attention backward then runs without float atomics
+(pn_msda_bwd_det_f32) and those six become reproducible too; the other six are built exactly as
+without the flag.
 
 Stops at the first configuration that fails or exceeds its time limit."""
 import argparse
@@ -24,6 +29,9 @@ sys.path.insert(0, ROOT)
 CONFIGS = ("tail", "tail_decoder", "tail_pixel_decoder", "tail_resnet", "tail_swin_last", "tail_swin_all_drop_path",
            "tail_device_targets", "tail_dropout", "baseline_feats", "baseline_image", "bbox_host",
            "bbox_device_targets")
+# the configurations whose backward passes pn_msda_bwd_f32's float atomics (labnotes R27.3)
+PD_TAPE = ("tail_pixel_decoder", "tail_resnet", "tail_swin_last", "tail_swin_all_drop_path",
+           "baseline_feats", "baseline_image")
 DEV = "cuda:0"
 
 
@@ -53,9 +61,10 @@ def pyramid(g, B, H, W, chans=(256, 512, 1024, 2048), strides=(4, 8, 16, 32)):
     return [torch.randn(B, c, H // s, W // s, generator=g).to(DEV) for c, s in zip(chans, strides)]
 
 
-def run(name):
+def run(name, deterministic=False):
     import torch
     import pairnet_amd as P
+    det_kw = dict(deterministic=True) if deterministic and name in PD_TAPE else {}
     torch.manual_seed(0)
     g = torch.Generator().manual_seed(2)
     gt_labels = [torch.tensor([3, 17, 90, 120, 3]), torch.tensor([5, 60, 7])]
@@ -75,7 +84,7 @@ def run(name):
         det.to(DEV)
         head, bb = det.bbox_head, det.backbone
         kw = dict(drop_path=True, seed=5, decay_mult={"backbone.": 0.0}) if "drop_path" in name else {}
-        tr = det.trainer(train_backbone=True, lr=1e-3, **kw)
+        tr = det.trainer(train_backbone=True, lr=1e-3, **kw, **det_kw)
         x = torch.randn(2, 3, H, W, generator=g).to(DEV)
         metas = [dict(img_shape=(H, W, 3), scale_factor=[1.0] * 4, batch_input_shape=(H, W))] * 2
         masks = [(torch.rand(len(l), H, W, generator=g) > 0.6).numpy() for l in gt_labels]
@@ -98,7 +107,7 @@ def run(name):
         if name == "tail_resnet":
             bb = kw["backbone"] = P.ResNet50Hip().to(DEV)
             x = torch.randn(2, 3, H, W, generator=g).to(DEV)
-        tr = P.TailTrainer(head, lr=1e-3, **kw)
+        tr = P.TailTrainer(head, lr=1e-3, **kw, **det_kw)
         step = lambda: tr.step(x, metas, gt_rels, gt_labels, masks, point_coords=pts)
     elif name.startswith("baseline"):
         H, W = 64, 96
@@ -118,7 +127,7 @@ def run(name):
             x = torch.randn(2, 3, H, W, generator=g).to(DEV)
         metas = [dict(img_shape=(H, W, 3), scale_factor=[1.5] * 4)] * 2
         masks = [(torch.rand(len(l), H // 2, W // 2, generator=g) > 0.6).to(torch.uint8) for l in gt_labels]
-        tr = P.BaselineTrainer(head, backbone=bb, lr=1e-3, seed=3)
+        tr = P.BaselineTrainer(head, backbone=bb, lr=1e-3, seed=3, **det_kw)
         step = lambda: tr.step(x, metas, gt_rels, gt_labels, masks)
     else:
         H, W = 128, 160
@@ -131,6 +140,8 @@ def run(name):
         tr = P.BBoxTrainer(head, lr=1e-3, device_targets=name == "bbox_device_targets")
         step = lambda: tr.step(x, metas, rels, [box, box[:3]], [gt_labels[0], gt_labels[1]])
     out = OrderedDict(config=name, names=digest(list(tr.names)), n_names=len(tr.names))
+    if deterministic:
+        out["deterministic"] = bool(det_kw)
     for k in ("seg_off", "seg_lr", "seg_wd"):
         out[k] = digest(getattr(tr, k))
     out["flat_p0"] = digest(tr.flat_p)
@@ -157,14 +168,17 @@ if __name__ == "__main__":
     ap.add_argument("--only", default=",".join(CONFIGS))
     ap.add_argument("--out", default=None)
     ap.add_argument("--limit", type=int, default=150, help="seconds per configuration")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="deterministic=True where there is a pixel-decoder tape")
     args = ap.parse_args()
     if args.config:
-        run(args.config)
+        run(args.config, args.deterministic)
         sys.exit(0)
     lines = []
     for name in args.only.split(","):
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", name],
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", name]
+                               + (["--deterministic"] if args.deterministic else []),
                                capture_output=True, text=True, timeout=args.limit)
         except subprocess.TimeoutExpired:
             sys.exit("%s: no result within %d s; stopping" % (name, args.limit))
