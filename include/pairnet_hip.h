@@ -1403,6 +1403,67 @@ int pn_box_match_cost_f32(const float* cls, const float* box, const int64_t* gt_
                           void* stream);
 
 /* -------------------------------------------------------------------------
+ * The triplet matching of PSGTrHead2's loss (csrc/tri_loss.hip; pair-net_amd/psgtr2_losses.py drives
+ * it): `_get_target_single` of relation_heads/psgtr_head2.py:879-1018 with `MaskHTriMatcher.assign`
+ * of approaches/matcher.py:29-102 under configs/psgtr/psgtr_r50_psg_plus.py:162-177, for every image
+ * of the batch.  The assignment is ONE pn_lsa_f32 launch over the B images; the seven loss terms
+ * behind it are pn_ce_avg_f32 and the per-mask point entries of csrc/seg_loss.hip, unchanged.
+ * Fixed-order reductions, no floating-point atomics.  Entries added at ABI 34 (adding entries is
+ * compatible).
+ *
+ * tab [B][8] int64 on the device, one row per image: {offset of its row-major Q x R_b block in
+ * `cost`, R_b, offset of its rows in gt_rels [rel_len][3] = (subject object, object object,
+ * predicate), offset of its objects in the concatenated ground truth (labels [SG], masks
+ * [SG][hg][wg]), G_b, offset of its min(Q, R_b) entries in row_ind / col_ind / matched, 0, 0}.
+ * ------------------------------------------------------------------------- */
+/* MaskHTriMatcher's cost (matcher.py:67-83; psgtr_head2.py:909-934 for the samples) of every image,
+ * laid out as pn_lsa_f32's table wants: for query q and relation k = (so, oo, p) of image b
+ *   cost[q][k] = s_cls + s_mask + s_dice + o_cls + o_mask + o_dice + r_cls, added left to right,
+ *   x_cls  = -softmax(logits[b][q])[label] * w           (ClassificationCost; label = gt_labels[so],
+ *            gt_labels[oo], p on sub_cls / obj_cls [B][Q][C1] and rel_cls [B][Q][Cr1])
+ *   x_mask = (sum_i BCE(x_i, 0) - sum_i x_i t_i) / Np * w        (CrossEntropyLossCost, sigmoid)
+ *   x_dice = (1 - (2 sum_i s_i t_i + eps) / (sum_i s_i + sum_i t_i + eps)) * w,  s = sigmoid(x)
+ * with x = the query's mask logits (sub_maps / obj_maps [B][Q][h][w], two bases) and t = the
+ * object's uint8 mask [hg][wg], both sampled (mmcv point_sample) at the image's points pts
+ * [B][Np][2], which subject and object, predictions and ground truth share (:909).  The mask and
+ * dice terms are computed once per (side, query, OBJECT) and gathered per relation: mask work is
+ * proportional to Q * G_b.  weights (HOST pointer, read before the launches) [9] = s_cls, s_mask,
+ * s_dice, o_cls, o_mask, o_dice, r_cls weights, then the s and o dice eps.  Scratch, written in
+ * full for every object / row in range: t [SG][Np], tsum [SG], stats [3][B * Q][2], pair
+ * [2][SG][Q][2], part [part_floats >= 4 (SG + B) Q pn_tri_pair_splits(B, Q, Np)] (the pair sums of
+ * every split of the points, added in ascending split order).  max_G / max_cells: the largest G_b
+ * and Q * R_b, known from shapes (they size the grids).  Five launches whatever B, sum R_b and
+ * sum G_b are.  A relation whose objects, predicate
+ * or labels are out of range gives NaN cells, as a NaN operand does (pn_lsa_f32 status 1); a table
+ * row outside a buffer leaves its block untouched. */
+int pn_tri_match_cost_f32(const float* sub_cls, const float* obj_cls, const float* rel_cls,
+                          const float* sub_maps, const float* obj_maps, const uint8_t* gt_masks,
+                          const float* pts, const int64_t* gt_rels, int64_t rel_len,
+                          const int64_t* gt_labels, int64_t SG, const int64_t* tab, int B, int Q,
+                          int C1, int Cr1, int h, int w, int hg, int wg, int Np, int max_G,
+                          int64_t max_cells, const float* weights, float* t, float* tsum,
+                          float* stats, float* pair, float* part, int64_t part_floats, float* cost,
+                          int64_t cost_len, void* stream);
+/* The number of point splits pn_tri_match_cost_f32 uses for its pair sums: a function of the shapes
+ * alone (whole 256-point chunks per split, at most 16), so the summation order is too. */
+int pn_tri_pair_splits(int B, int Q, int Np);
+/* The targets behind the assignment (psgtr_head2.py:967-997, MaskPseudoSampler: positives in
+ * ascending query order): labels [3][B * Q] int64 = sub | obj | rel labels with the fills C, C, Cr
+ * (:971-984: the relation fill is num_relations, the LAST index); matched [M][4] int64 = (image,
+ * query, subject object, object object), objects counted over the batch; side_rows [2][M][4] int64 =
+ * (0, image, query, object) per side, the row layout pn_uncertain_points_f32 and
+ * pn_mask_point_loss_f32 read with L = 1; rel_idx [M] int64 = the matched relation's index in its
+ * image; mcount [1] = the matched rows written; M = sum_b min(Q, R_b).  status [1] int32: the OR of
+ * pn_lsa_f32's status of every image, | 4 a relation's object outside [0, G_b), predicate outside
+ * [1, Cr], object label outside [0, C) or an assignment index out of range, | 8 a table row out of
+ * range.  An image with a non-zero status keeps its fills and its matched rows -1. */
+int pn_tri_targets(const int64_t* tab, const int32_t* row_ind, const int32_t* col_ind,
+                   int64_t out_len, const int32_t* lsa_status, const int64_t* gt_rels,
+                   int64_t rel_len, const int64_t* gt_labels, int64_t SG, int B, int Q, int C, int Cr,
+                   int64_t M, int64_t* labels, int64_t* matched, int64_t* side_rows,
+                   int64_t* rel_idx, int32_t* mcount, int32_t* status, void* stream);
+
+/* -------------------------------------------------------------------------
  * Backward of the mask logits (csrc/seg_grad.hip): the two products that differentiate
  *   mask_pred = torch.einsum("bqc,bchw->bqhw", mask_embed, mask_feature)
  * (pairnet_head.py:236-243 / baseline.py:254-296, once per decoder layer) from the COMPACT gradient

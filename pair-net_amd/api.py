@@ -2,6 +2,7 @@
 from .config import (ConfigDict, baseline_head_cfg, baseline_r50, bbox_head_cfg,  # noqa: F401
                      channel_mapper_cfg, cross_r101_vg, load_config,
                      pairnet_head_cfg, pairnet_r50, pairnet_swin, psgtr2_head_cfg, psgtr2_r50,
+                     psgtr2_train_cfg,
                      swin_backbone_cfg, test_pipeline_cfg, train_pipeline_cfg)
 from .psgtr_head2 import PSGTrHead2  # noqa: F401
 from .backbone import ResNet50Hip  # noqa: F401
@@ -20,6 +21,7 @@ from .bbox_train import BBoxTrainer  # noqa: F401
 from .bbox_losses import CrossHeadBBoxLoss  # noqa: F401
 from .seg_losses import Mask2FormerLoss  # noqa: F401
 from .baseline_losses import BaselineRelationLoss  # noqa: F401
+from .psgtr2_losses import PSGTrHead2Loss  # noqa: F401
 from .preprocess import TestPipeline  # noqa: F401
 from .train_pipeline import AugParams, HalfSizeMasks, TrainPipeline  # noqa: F401
 from .detector import (PSGTr, Result, ResultStreamer, build_detector, load_checkpoint,  # noqa: F401
@@ -37,4 +39,5 @@ __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "Cros
            "CrossHeadBBox", "ChannelMapper", "bbox_head_cfg", "channel_mapper_cfg", "cross_r101_vg",
            "TripletEvaluator", "SceneGraphMetrics", "StreamingEvaluator", "PanopticQuality", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "SwinStagesGrad", "SegmenterHeadGrad", "BaselineHeadGrad", "SegPixelDecoderGrad", "TailTrainer", "BaselineTrainer", "FfnDropout",
            "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg", "Mask2FormerLoss",
-           "BaselineRelationLoss", "BBoxTailGrad", "BBoxTrainer", "CrossHeadBBoxLoss"]
+           "BaselineRelationLoss", "BBoxTailGrad", "BBoxTrainer", "CrossHeadBBoxLoss",
+           "PSGTrHead2Loss", "psgtr2_train_cfg"]

@@ -213,10 +213,25 @@ def baseline_r50():
     return cfg
 
 
+def psgtr2_train_cfg():
+    """`train_cfg` of configs/psgtr/psgtr_r50_psg_plus.py:162-177: the point sampling of the mask
+    terms and MaskHTriMatcher's seven costs."""
+    mask = dict(type="CrossEntropyLossCost", weight=5.0, use_sigmoid=True)
+    dice = dict(type="DiceCost", weight=5.0, pred_act=True, eps=1.0)
+    cls = dict(type="ClassificationCost", weight=2.0)
+    return ConfigDict(
+        num_points=12544, oversample_ratio=3.0, importance_sample_ratio=0.75,
+        sampler=dict(type="MaskPseudoSampler"),
+        assigner=dict(type="MaskHTriMatcher", s_cls_cost=dict(cls), s_mask_cost=dict(mask),
+                      s_dice_cost=dict(dice), o_cls_cost=dict(cls), o_mask_cost=dict(mask),
+                      o_dice_cost=dict(dice), r_cls_cost=dict(cls)))
+
+
 def psgtr2_r50():
     """`model` section: PSGTr(ResNet-50, PSGTrHead2)."""
     cfg = pairnet_r50()
     cfg["bbox_head"] = psgtr2_head_cfg()
+    cfg["train_cfg"] = psgtr2_train_cfg()
     return cfg
 
 

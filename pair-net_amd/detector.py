@@ -417,10 +417,10 @@ class PSGTr:
             raise NotImplementedError("bbox_head.type must be one of %s" % sorted(heads))
         # (mmdet's SingleStageDetector hands the model-level train_cfg to the head -- the
         # base class psgtr.py:84-86 calls; here
-        # CrossHead2 and CrossHeadBBox read it, for their losses)
+        # CrossHead2, CrossHeadBBox and PSGTrHead2 read it, for their losses)
         self.bbox_head = heads[head_type](**head_cfg,
                                           train_cfg=train_cfg if head_type in (
-                                              "CrossHead2", "CrossHeadBBox") else None,
+                                              "CrossHead2", "CrossHeadBBox", "PSGTrHead2") else None,
                                           test_cfg=test_cfg or dict(max_per_img=100))
         self.num_classes = self.bbox_head.num_classes
         self.test_pipeline = None     # built by detect() (or set a preprocess.TestPipeline)
@@ -554,6 +554,22 @@ class PSGTr:
         finally:
             head.return_all_layers = old
         return head.full_losses(*outs, gt_rels, None, gt_labels, gt_masks, img_metas, **kw)
+
+    @torch.no_grad()
+    def val_triplet_losses(self, img, img_metas, gt_rels, gt_labels, gt_masks, **kw):
+        """The loss dict of a head that matches triplets (`PSGTrHead2.triplet_losses`: s_loss_cls,
+        o_loss_cls, r_loss_cls and the mask / dice terms of both sides,
+        relation_heads/psgtr_head2.py:447-594) as validation values, shaped like `val_full_losses`:
+        extract_feat -> prepared ground-truth masks -> head forward -> `triplet_losses`.  Keywords
+        go to `PSGTrHead2Loss.loss` (`grads={}`, `points=`, `seed=`, `step=`, `num_total_masks=`)."""
+        head = self.bbox_head
+        if not hasattr(head, "triplet_losses"):
+            raise NotImplementedError("%s has no triplet loss dict here (PSGTrHead2 does)"
+                                      % type(head).__name__)
+        x = self.extract_feat(img)
+        gt_masks = self._prepare_gt_masks(img, gt_masks)
+        outs = head.forward(x, img_metas)
+        return head.triplet_losses(*outs, gt_rels, None, gt_labels, gt_masks, img_metas, **kw)
 
     def _prepare_gt_masks(self, img, gt_masks):
         """PSGTr.forward_train's ground-truth mask preparation (psgtr.py:126-141): zero-pad to the

@@ -259,6 +259,11 @@ _SIGS = {
     "pn_bilinear_nhwc_bwd_f32": (C.c_int, [_vp, _vp] + [_i32] * 7 + [_i64, _i64, _vp]),
     "pn_groupnorm_act_nhwc_bwd_f32": (C.c_int, [_vp] * 10 + [_i32, _i64, _i32, _f32, _i32, _i32,
                                                              _i64, _i64, _vp]),
+    "pn_tri_match_cost_f32": (C.c_int, [_vp] * 8 + [_i64, _vp, _i64, _vp] + [_i32] * 10 + [_i64] +
+                              [_vp] * 6 + [_i64, _vp, _i64, _vp]),
+    "pn_tri_pair_splits": (C.c_int, [_i32, _i32, _i32]),
+    "pn_tri_targets": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32,
+                                 _i32, _i64] + [_vp] * 7),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 34  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
@@ -1963,6 +1968,76 @@ def box_match_cost(cls, box, gt_labels, gt_bboxes, factor, tab, cost, max_cells,
                                        cost.numel(), int(max_cells), B, Q, nc, w_cls, w_reg, w_iou,
                                        alpha, gamma, eps, iou_eps, _stream()),
            "pn_box_match_cost_f32")
+
+
+# ---- PSGTrHead2's triplet matching (csrc/tri_loss.hip; composed in psgtr2_losses.py) --------------
+# sites of the counter-based draws (pn_uniform_f32), clear of seg_losses.py's 4 * layer + {0, 1, 2}
+TRI_SITE_ASSIGN, TRI_SITE_SUB_CANDIDATES, TRI_SITE_SUB_TAIL = 1024, 1025, 1026
+TRI_SITE_OBJ_CANDIDATES, TRI_SITE_OBJ_TAIL = 1027, 1028
+TRI_STATUS_RANGE, TRI_STATUS_TABLE = 4, 8
+
+
+def tri_match_cost_scratch(B, Q, SG, Np, device):
+    """The scratch of `tri_match_cost` for B images, Q queries, SG objects in all, Np points."""
+    f32 = lambda *s: torch.empty(*s, device=device, dtype=torch.float32)
+    return dict(t=f32(SG, Np), tsum=f32(SG), stats=f32(3, B * Q, 2), pair=f32(2, SG, Q, 2),
+                part=f32(4 * (SG + B) * Q * lib().pn_tri_pair_splits(B, Q, Np)))
+
+
+def tri_match_cost(sub_cls, obj_cls, rel_cls, sub_maps, obj_maps, gt_masks, pts, gt_rels, gt_labels,
+                   tab, weights, max_G, max_cells, cost, scratch=None):
+    """include/pairnet_hip.h: every image's [Q, R_b] MaskHTriMatcher cost block of the flat `cost`,
+    five launches.  sub_cls / obj_cls [B, Q, C1], rel_cls [B, Q, Cr1], sub_maps / obj_maps
+    [B, Q, h, w] fp32; gt_masks [SG, hg, wg] uint8; pts [B, Np, 2]; gt_rels [., 3] and gt_labels [SG]
+    int64; tab [B, 8] int64; weights: nine host floats (seven cost weights, two dice eps).
+    -> the scratch dict(t [SG, Np], tsum [SG], stats [3, B * Q, 2], pair [2, SG, Q, 2], part: the
+    pair sums of every point split, `tri_match_cost_scratch`)."""
+    B, Q, C1 = sub_cls.shape
+    Cr1 = rel_cls.shape[2]
+    h, w = sub_maps.shape[2:]
+    SG, hg, wg = gt_masks.shape
+    Np = pts.shape[1]
+    assert obj_cls.shape == (B, Q, C1) and rel_cls.shape[:2] == (B, Q) and tab.shape == (B, 8)
+    assert sub_maps.shape == (B, Q, h, w) and obj_maps.shape == (B, Q, h, w)
+    assert pts.shape == (B, Np, 2) and gt_masks.dtype == torch.uint8 and gt_labels.numel() == SG
+    assert gt_rels.dim() == 2 and gt_rels.shape[1] == 3 and len(weights) == 9
+    assert all(t.is_contiguous() for t in (sub_cls, obj_cls, rel_cls, sub_maps, obj_maps, gt_masks,
+                                           pts, gt_rels, gt_labels, tab, cost))
+    dev = sub_cls.device
+    s = scratch or tri_match_cost_scratch(B, Q, SG, Np, dev)
+    assert s["t"].shape == (SG, Np) and s["tsum"].numel() == SG and s["pair"].shape == (2, SG, Q, 2)
+    assert s["stats"].shape == (3, B * Q, 2) and all(v.is_contiguous() for v in s.values())
+    assert s["part"].numel() >= 4 * (SG + B) * Q * lib().pn_tri_pair_splits(B, Q, Np)
+    wts = (C.c_float * 9)(*[float(v) for v in weights])
+    _check(lib().pn_tri_match_cost_f32(
+        _ptr(sub_cls), _ptr(obj_cls), _ptr(rel_cls), _ptr(sub_maps), _ptr(obj_maps),
+        _ptr(gt_masks, torch.uint8), _ptr(pts), _ptr(gt_rels, torch.int64), gt_rels.shape[0],
+        _ptr(gt_labels, torch.int64), SG, _ptr(tab, torch.int64), B, Q, C1, Cr1, h, w, hg, wg, Np,
+        int(max_G), int(max_cells), C.cast(wts, C.c_void_p), _ptr(s["t"]), _ptr(s["tsum"]),
+        _ptr(s["stats"]), _ptr(s["pair"]), _ptr(s["part"]), s["part"].numel(), _ptr(cost),
+        cost.numel(), _stream()),
+        "pn_tri_match_cost_f32")
+    return s
+
+
+def tri_targets(tab, row_ind, col_ind, lsa_status, gt_rels, gt_labels, Q, C, Cr, labels, matched,
+                side_rows, rel_idx, mcount, status):
+    """include/pairnet_hip.h: labels [3, B * Q], matched [M, 4], side_rows [2, M, 4], rel_idx [M]
+    int64, mcount / status [1] int32 from the B assignments."""
+    B = tab.shape[0]
+    M = matched.shape[0]
+    assert tab.shape == (B, 8) and tab.is_contiguous() and labels.shape == (3, B * Q)
+    assert matched.shape == (M, 4) and side_rows.shape == (2, M, 4) and rel_idx.numel() == M
+    assert row_ind.numel() == col_ind.numel() and lsa_status.numel() >= B
+    assert all(t.is_contiguous() for t in (labels, matched, side_rows, rel_idx, gt_rels, gt_labels))
+    _check(lib().pn_tri_targets(_ptr(tab, torch.int64), _ptr(row_ind, torch.int32),
+                                _ptr(col_ind, torch.int32), row_ind.numel(),
+                                _ptr(lsa_status, torch.int32), _ptr(gt_rels, torch.int64),
+                                gt_rels.shape[0], _ptr(gt_labels, torch.int64), gt_labels.numel(), B,
+                                Q, C, Cr, M, _ptr(labels, torch.int64), _ptr(matched, torch.int64),
+                                _ptr(side_rows, torch.int64), _ptr(rel_idx, torch.int64),
+                                _ptr(mcount, torch.int32), _ptr(status, torch.int32), _stream()),
+           "pn_tri_targets")
 
 
 # ---- the mask logits' backward (csrc/seg_grad.hip; composed in seg_grad.py) -----------------------

@@ -26,7 +26,8 @@ from .head import CrossHead2
 
 
 class PSGTrHead2(CrossHead2):
-    """Drop-in for the reference's `PSGTrHead2` (inference half)."""
+    """Drop-in for the reference's `PSGTrHead2`: inference, and the loss values with their logit
+    gradients (`triplet_losses`, psgtr2_losses.py); backward behind the logits is not built."""
 
     _pair_masks_fusable = False      # (CrossHead2.fused_pair_masks: not for this head)
 
@@ -43,6 +44,14 @@ class PSGTrHead2(CrossHead2):
                          num_obj_query=num_obj_query, num_rel_query=num_obj_query,
                          use_mask=use_mask, n_heads=n_heads, embed_dims=embed_dims,
                          train_cfg=None, **kwargs)
+        # the loss options (psgtr_head2.py:24-86; configs/psgtr/psgtr_r50_psg_plus.py:118-177), kept
+        # as given and validated on first use (`triplet_losses`)
+        self._tri_loss_cfg = dict(bg_cls_weight=bg_cls_weight, train_cfg=train_cfg,
+                                  sub_loss_cls=sub_loss_cls, sub_loss_mask=sub_loss_mask,
+                                  sub_loss_dice=sub_loss_dice, obj_loss_cls=obj_loss_cls,
+                                  obj_loss_mask=obj_loss_mask, obj_loss_dice=obj_loss_dice,
+                                  rel_loss_cls=rel_loss_cls)
+        self._tri_loss = None
 
     # ------------------------------------------------------------------ params
     def param_shapes(self):
@@ -119,6 +128,28 @@ class PSGTrHead2(CrossHead2):
     def forward_head(self, decoder_out, mask_feature, attn_mask_target_size):
         raise NotImplementedError("PSGTrHead2.forward_head (six outputs, psgtr_head2.py:288) is "
                                   "internal to forward() here")
+
+    # ------------------------------------------------------- loss values and logit gradients
+    def triplet_losses(self, all_cls_scores, all_mask_preds, gt_rels_list, gt_bboxes_list,
+                       gt_labels_list, gt_masks_list, img_metas, gt_bboxes_ignore=None, **kw):
+        """The reference's `loss` dict (psgtr_head2.py:447-594, its argument order): s_loss_cls,
+        o_loss_cls, r_loss_cls, s_loss_mask, o_loss_mask, s_loss_dice, o_loss_dice from the two dicts
+        `forward` returns (psgtr2_losses.py).  Values; `grads={}` receives "sub", "obj", "rel",
+        "mask_rows", "sub_mask" and "obj_mask" (d sum / d logits); `points=`, `seed=`, `step=`,
+        `num_total_masks=` fix the draws and the normaliser.  An image without a ground-truth
+        relation raises ValueError.  `triplet_status()` holds the device status word."""
+        if not self.use_mask:
+            # (the reference's use_mask=False branch runs into an undefined name, :520)
+            raise NotImplementedError("PSGTrHead2.triplet_losses with use_mask=False")
+        if self._tri_loss is None:
+            from .psgtr2_losses import PSGTrHead2Loss
+            self._tri_loss = PSGTrHead2Loss(self.num_classes, self.num_relations,
+                                            self.num_obj_query, **self._tri_loss_cfg)
+        return self._tri_loss.loss(all_cls_scores, all_mask_preds, gt_rels_list, gt_bboxes_list,
+                                   gt_labels_list, gt_masks_list, img_metas, gt_bboxes_ignore, **kw)
+
+    def triplet_status(self):
+        return None if self._tri_loss is None else self._tri_loss.assign_status
 
     # ------------------------------------------------------- post-processing
     @torch.no_grad()
