@@ -1494,6 +1494,26 @@ int pn_mask_feature_grad_f32(const float* G, const float* me, const int64_t* mas
                              const int32_t* table, int64_t table_len, int M, int B, int64_t P,
                              int64_t me_rows, float* dMF, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Backward of PSGTrHead2's three class heads (csrc/tri_grad.hip; psgtr_head2.py:309-324:
+ * sub_cls_embed, obj_cls_embed, rel_cls_embed on the same post-normed rows qn [N][256], N = B * Q):
+ *   dqn[n][:]  = (add ? dqn[n][:] : 0) + sum_j dsub[n][j] Wsub[j][:] + sum_j dobj[n][j] Wobj[j][:]
+ *                                      + sum_j drel[n][j] Wrel[j][:]
+ *   dW_h[j][:] = sum_n d_h[n][j] qn[n][:]      db_h[j] = sum_n d_h[n][j]      h in {sub, obj, rel}
+ * dsub / dobj [N][C1], drel [N][Cr1] contiguous as the loss writes them (no padding), W_h / dW_h
+ * [width][256] in the reference's layout, db_h [width]; dW_h and db_h are written whole.  Two
+ * launches on v_mfma_f32_32x32x2_f32 (fp32 operands and accumulation): a row-tile kernel for dqn
+ * that contracts over the columns of sub, obj, rel in this order, each ascending, and a
+ * column-tile kernel for dW / db that contracts over n ascending.  Ragged edges are predicated in
+ * the kernels; no float atomics; the same inputs give the same bits.  channels == 256, N <= 4096,
+ * C1 <= 256, Cr1 <= 64, add in {0, 1}; anything else returns -1 before a launch.
+ * ------------------------------------------------------------------------- */
+int pn_triplet_heads_bwd_f32(const float* dsub, const float* dobj, const float* drel,
+                             const float* qn, const float* Wsub, const float* Wobj,
+                             const float* Wrel, float* dqn, float* dWsub, float* dbsub,
+                             float* dWobj, float* dbobj, float* dWrel, float* dbrel, int N,
+                             int channels, int C1, int Cr1, int add, void* stream);
+
 /* ---- backward of the pixel decoder's FPN branch (MSDeformAttnPixelDecoder.forward behind
  * pairnet_head.py:262: lateral_convs.0 -> + bilinear-up(finest memory) -> output_convs.0 ->
  * mask_feature; pair-net_amd/seg_grad.py SegPixelDecoderGrad).  No float atomics: bitwise

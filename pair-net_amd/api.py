@@ -14,10 +14,12 @@ from .head import CrossHead2  # noqa: F401
 from .pipeline import PipelinedHead  # noqa: F401
 from .grad import (BackboneGrad, FfnDropout, HeadGrad, PixelDecoderGrad,  # noqa: F401
                    RelationTailGrad, SwinBackboneGrad, SwinStagesGrad, BBoxTailGrad)
-from .seg_grad import BaselineHeadGrad, SegmenterHeadGrad, SegPixelDecoderGrad  # noqa: F401
+from .seg_grad import (BaselineHeadGrad, PSGTr2HeadGrad, SegmenterHeadGrad,  # noqa: F401
+                       SegPixelDecoderGrad)
 from .train import TailTrainer  # noqa: F401
 from .baseline_train import BaselineTrainer  # noqa: F401
 from .bbox_train import BBoxTrainer  # noqa: F401
+from .psgtr2_train import PSGTr2Trainer  # noqa: F401
 from .bbox_losses import CrossHeadBBoxLoss  # noqa: F401
 from .seg_losses import Mask2FormerLoss  # noqa: F401
 from .baseline_losses import BaselineRelationLoss  # noqa: F401
@@ -40,4 +42,4 @@ __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "Cros
            "TripletEvaluator", "SceneGraphMetrics", "StreamingEvaluator", "PanopticQuality", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "SwinStagesGrad", "SegmenterHeadGrad", "BaselineHeadGrad", "SegPixelDecoderGrad", "TailTrainer", "BaselineTrainer", "FfnDropout",
            "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg", "Mask2FormerLoss",
            "BaselineRelationLoss", "BBoxTailGrad", "BBoxTrainer", "CrossHeadBBoxLoss",
-           "PSGTrHead2Loss", "psgtr2_train_cfg"]
+           "PSGTrHead2Loss", "psgtr2_train_cfg", "PSGTr2HeadGrad", "PSGTr2Trainer"]

@@ -742,6 +742,63 @@ class PSGTr:
         return dict(loss=loss, log_vars={k: float(v) for k, v in list(out.items()) + [("loss", loss)]},
                     num_samples=len(img_metas))
 
+    def triplet_trainer(self, train_backbone=None, **kw):
+        """`trainer()` for the triplet head: builds and keeps a `pairnet_amd.PSGTr2Trainer` over
+        every parameter the reference's `losses.backward()` reaches behind a `PSGTrHead2`
+        (psgtr2_train.py).  `train_backbone`: None (default) / True trains a ResNet
+        backbone's stages 2-4 (`step` then takes the image), False leaves the backbone frozen
+        (`step` takes its features); True with a Swin backbone raises.  Other keywords go to
+        `PSGTr2Trainer` (lr, lr_mult, decay_mult, seed, masked_keysplit_min_keys,
+        `deterministic=True` for a bitwise reproducible step without float atomics).  `trainer()`,
+        `train_step()` and the other heads' `val_*losses()` keep refusing this head."""
+        from .backbone import ResNet50Hip
+        from .psgtr2_train import PSGTr2Trainer
+        if type(self.bbox_head) is not PSGTrHead2:
+            raise NotImplementedError("triplet_trainer is built for PSGTrHead2 only (%s: trainer() / "
+                                      "full_trainer() / box_trainer())"
+                                      % type(self.bbox_head).__name__)
+        resnet = isinstance(self.backbone, ResNet50Hip)
+        if train_backbone is None:
+            train_backbone = resnet
+        if train_backbone and not resnet:
+            raise NotImplementedError("triplet_trainer trains a ResNet50Hip backbone; a %s backbone "
+                                      "is out of scope (train_backbone=False keeps it frozen)"
+                                      % type(self.backbone).__name__)
+        self._triplet_trainer = PSGTr2Trainer(self.bbox_head,
+                                              backbone=self.backbone if train_backbone else None,
+                                              **kw)
+        return self._triplet_trainer
+
+    def triplet_train_step(self, img, img_metas=None, gt_rels=None, gt_bboxes=None, gt_labels=None,
+                           gt_masks=None, num_total_masks=None):
+        """`train_step` for the triplet head, the same two call forms as `full_train_step`:
+        `forward_train`'s argument order -> the seven loss terms + `grad_norm` + `assign_status`
+        (device scalars), or `(data_batch, optimizer)` -> mmdet's dict(loss, log_vars, num_samples)
+        with `loss` the sum of the terms whose name contains "loss".  Runs `triplet_trainer().step`
+        -- the trainer an earlier `triplet_trainer(...)` call built if there is one, else the
+        default one."""
+        mmdet_form = isinstance(img, dict)
+        if mmdet_form:
+            data = img
+            unwrap = lambda v: getattr(v, "data", v)        # (mmcv DataContainer)
+            first = lambda v: v[0] if isinstance(v, (list, tuple)) and len(v) == 1 and \
+                isinstance(v[0], (list, tuple)) else v
+            img = unwrap(data["img"])
+            if isinstance(img, (list, tuple)):
+                img = img[0]
+            img_metas = first(unwrap(data["img_metas"]))
+            gt_rels, gt_labels = first(unwrap(data["gt_rels"])), first(unwrap(data["gt_labels"]))
+            gt_masks = first(unwrap(data["gt_masks"]))
+        tr = getattr(self, "_triplet_trainer", None) or self.triplet_trainer()
+        gt_masks = self._prepare_gt_masks(img, gt_masks)
+        x = img if tr.backbone is not None else self.extract_feat(img)
+        out = tr.step(x, img_metas, gt_rels, gt_labels, gt_masks, num_total_masks=num_total_masks)
+        if not mmdet_form:
+            return out
+        loss = sum(v for k, v in out.items() if "loss" in k)
+        return dict(loss=loss, log_vars={k: float(v) for k, v in list(out.items()) + [("loss", loss)]},
+                    num_samples=len(img_metas))
+
     def box_trainer(self, **kw):
         """`trainer()` for the box head: builds and keeps a `pairnet_amd.BBoxTrainer` over the
         parameters the reference's `losses.backward()` reaches behind a `CrossHeadBBox` -- the

@@ -264,6 +264,7 @@ _SIGS = {
     "pn_tri_pair_splits": (C.c_int, [_i32, _i32, _i32]),
     "pn_tri_targets": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32,
                                  _i32, _i64] + [_vp] * 7),
+    "pn_triplet_heads_bwd_f32": (C.c_int, [_vp] * 14 + [_i32] * 5 + [_vp]),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 34  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
@@ -2127,3 +2128,41 @@ def mask_feature_grad(G, me, mask_rows, table, T, dMF):
                                           _ptr(table, torch.int32), table.numel(), M, B, P,
                                           me.shape[0], _ptr(dMF), _stream()),
            "pn_mask_feature_grad_f32")
+
+
+# ---- PSGTrHead2's three class heads, backward (csrc/tri_grad.hip; composed in seg_grad.py) --------
+TRI_HEADS_MAX_ROWS, TRI_HEADS_MAX_C1, TRI_HEADS_MAX_CR1 = 4096, 256, 64
+
+
+def tri_heads_bwd(dsub, dobj, drel, qn, Wsub, Wobj, Wrel, dqn, dWsub, dbsub, dWobj, dbobj, dWrel,
+                  dbrel, add=False):
+    """include/pairnet_hip.h, `pn_triplet_heads_bwd_f32`: dsub / dobj [N, C + 1], drel [N, Cr + 1] as
+    the loss wrote them, qn [N, 256], the three weights in the reference layout -> dqn [N, 256]
+    (`add`: onto what it holds) and the three dW [width, 256] / db [width], written whole.  Two
+    launches, bitwise reproducible.  Shapes beyond the kernels' limits raise NotImplementedError."""
+    if dsub.dim() != 2 or dobj.dim() != 2 or drel.dim() != 2 or qn.dim() != 2:
+        raise ValueError("dsub / dobj [N, C + 1], drel [N, Cr + 1], qn [N, channels]")
+    N, C1 = dsub.shape
+    Cr1, ch = drel.shape[1], qn.shape[1]
+    if ch != 256:
+        raise NotImplementedError("256 channels per query row, got %d" % ch)
+    if N > TRI_HEADS_MAX_ROWS:
+        raise NotImplementedError("B * Q <= %d rows per call" % TRI_HEADS_MAX_ROWS)
+    if C1 > TRI_HEADS_MAX_C1:
+        raise NotImplementedError("C + 1 <= %d object classes per call" % TRI_HEADS_MAX_C1)
+    if Cr1 > TRI_HEADS_MAX_CR1:
+        raise NotImplementedError("Cr + 1 <= %d relation classes per call" % TRI_HEADS_MAX_CR1)
+    if N <= 0 or C1 <= 0 or Cr1 <= 0:
+        raise ValueError("no rows / classes")
+    for name, t, shape in (("dsub", dsub, (N, C1)), ("dobj", dobj, (N, C1)), ("drel", drel, (N, Cr1)),
+                           ("qn", qn, (N, 256)), ("dqn", dqn, (N, 256)),
+                           ("Wsub", Wsub, (C1, 256)), ("Wobj", Wobj, (C1, 256)),
+                           ("Wrel", Wrel, (Cr1, 256)), ("dWsub", dWsub, (C1, 256)),
+                           ("dWobj", dWobj, (C1, 256)), ("dWrel", dWrel, (Cr1, 256)),
+                           ("dbsub", dbsub, (C1,)), ("dbobj", dbobj, (C1,)), ("dbrel", dbrel, (Cr1,))):
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("%s: contiguous %s, got %s" % (name, list(shape), tuple(t.shape)))
+    _check(lib().pn_triplet_heads_bwd_f32(
+        _ptr(dsub), _ptr(dobj), _ptr(drel), _ptr(qn), _ptr(Wsub), _ptr(Wobj), _ptr(Wrel), _ptr(dqn),
+        _ptr(dWsub), _ptr(dbsub), _ptr(dWobj), _ptr(dbobj), _ptr(dWrel), _ptr(dbrel), N, 256, C1, Cr1,
+        int(bool(add)), _stream()), "pn_triplet_heads_bwd_f32")

@@ -299,6 +299,9 @@ class PSGTrHead2Loss:
         idx_pred = torch.where(ok, matched[:, 0] * Q + matched[:, 1], matched[:, 0])
         out_m, g_mask = [], []
         ntm = 0.0 if num_total_masks is None else float(num_total_masks)
+        # (both sides' mask gradients are the halves of ONE buffer: `PSGTr2HeadGrad.backward` reads
+        # them as the [2 M, h * w] operand of the mask products without a copy)
+        g_both = f32(2, M, h, w) if grads is not None else None
         sites = ((hip.TRI_SITE_SUB_CANDIDATES, hip.TRI_SITE_SUB_TAIL),
                  (hip.TRI_SITE_OBJ_CANDIDATES, hip.TRI_SITE_OBJ_TAIL))
         for s, (name, maps) in enumerate((("sub", s_seg), ("obj", o_seg))):
@@ -346,7 +349,7 @@ class PSGTrHead2Loss:
                 self.last.update({name + "_points": pts, name + "_x": x, name + "_t": t,
                                   name + "_sums": sums, name + "_coef": coef})
             if grads is not None:
-                g = f32(M, h, w)
+                g = g_both[s]
                 scr = i32(hip.point_scatter_scratch_ints(M, Np, h, w))
                 hip.point_scatter_grad(coef, pts, g, scr)
                 g_mask.append(g)

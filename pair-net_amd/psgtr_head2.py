@@ -26,8 +26,10 @@ from .head import CrossHead2
 
 
 class PSGTrHead2(CrossHead2):
-    """Drop-in for the reference's `PSGTrHead2`: inference, and the loss values with their logit
-    gradients (`triplet_losses`, psgtr2_losses.py); backward behind the logits is not built."""
+    """Drop-in for the reference's `PSGTrHead2`: inference, the loss values with their logit
+    gradients (`triplet_losses`, psgtr2_losses.py) and the backward behind the logits
+    (`triplet_backward`: `PSGTr2HeadGrad` then `SegPixelDecoderGrad`, seg_grad.py) -- every parameter
+    the reference's `losses.backward()` reaches; `PSGTr2Trainer` (psgtr2_train.py) is the step."""
 
     _pair_masks_fusable = False      # (CrossHead2.fused_pair_masks: not for this head)
 
@@ -52,6 +54,8 @@ class PSGTrHead2(CrossHead2):
                                   obj_loss_mask=obj_loss_mask, obj_loss_dice=obj_loss_dice,
                                   rel_loss_cls=rel_loss_cls)
         self._tri_loss = None
+        self._tri_tape = None
+        self._segpd_tape = None
 
     # ------------------------------------------------------------------ params
     def param_shapes(self):
@@ -150,6 +154,37 @@ class PSGTrHead2(CrossHead2):
 
     def triplet_status(self):
         return None if self._tri_loss is None else self._tri_loss.assign_status
+
+    # ------------------------------------------------------- backward behind the logits
+    def triplet_backward(self, grads, feats, pl=None, need_dc2=False, deterministic=False):
+        """The six `grads` of `triplet_losses(..., grads={})` carried back through the head
+        (`PSGTr2HeadGrad`: the three class heads, `obj_mask_embed` on both query sets, `post_norm`,
+        the nine masked layers) and its (dmem, dMF) on through the pixel decoder, FPN branch
+        included (`SegPixelDecoderGrad`) -> (dfeats, {reference parameter name: gradient}) with
+        dfeats = [d C5, d C4, d C3, d C2 or None without `need_dc2`] (what `BackboneGrad` takes):
+        the counterpart of `CrossHeadBaseline.full_backward`, with its known limitation (the pixel
+        decoder's tape runs its own exact-fp32 forward).  `pl`: the plan of the forward whose outputs
+        the loss saw (default: the last one).  `deterministic`: the deformable-attention backward
+        without float atomics."""
+        pl = pl if pl is not None else getattr(self, "_last_plan", None)
+        if pl is None:
+            raise RuntimeError("triplet_backward needs a forward first")
+        if self._tri_loss is None or self._tri_loss.last is None:
+            raise RuntimeError("triplet_backward needs the grads of a triplet_losses call")
+        from .seg_grad import PSGTr2HeadGrad, SegPixelDecoderGrad
+        if self._tri_tape is None:
+            self._tri_tape = PSGTr2HeadGrad(self)
+        self._tri_tape.forward_from_plan(pl)
+        dmem, dMF, g_head = self._tri_tape.backward(grads, counts=self._tri_loss.last["counts"])
+        if self._segpd_tape is None:
+            self._segpd_tape = SegPixelDecoderGrad(self)
+        self._segpd_tape.deterministic = bool(deterministic)
+        self._segpd_tape.forward(feats)
+        dfeats, g_pd = self._segpd_tape.backward(dmem, dMF, need_dc2=need_dc2)
+        assert not set(g_head) & set(g_pd)
+        out = dict(g_head)
+        out.update(g_pd)
+        return dfeats, out
 
     # ------------------------------------------------------- post-processing
     @torch.no_grad()

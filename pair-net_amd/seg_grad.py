@@ -31,15 +31,20 @@ scores, the two update MLPs and the six relation decoder layers (whose cross-att
 a memory level is csrc/attn_grad.hip's key-split kernel), their shares added into the final queries'
 gradient, dmem and `level_embed`.
 
+`PSGTr2HeadGrad` is the same trunk under `PSGTrHead2`'s heads: no deep supervision, one head chain
+over the last layer's output and the initial queries (`obj_mask_embed` is used on both), the three
+ragged class heads' backward in csrc/tri_grad.hip's two launches.
+
 Not carried further here: the backbone below the feature gradients (`BackboneGrad` takes them) and
-the optimizer step (`BaselineTrainer`, baseline_train.py, runs both), `reduce_mean` across ranks.
+the optimizer step (`BaselineTrainer`, baseline_train.py, and `PSGTr2Trainer`, psgtr2_train.py, run
+both), `reduce_mean` across ranks.
 """
 import torch
 
 from . import hip
 from .grad import HeadGrad, PixelDecoderGrad, RelationTailGrad
 
-__all__ = ["SegmenterHeadGrad", "BaselineHeadGrad", "SegPixelDecoderGrad"]
+__all__ = ["SegmenterHeadGrad", "BaselineHeadGrad", "PSGTr2HeadGrad", "SegPixelDecoderGrad"]
 
 
 class SegmenterHeadGrad(HeadGrad):
@@ -108,12 +113,10 @@ class SegmenterHeadGrad(HeadGrad):
             out["mask"] = mask
         return out
 
-    @torch.no_grad()
-    @hip.on_device
-    def forward_from_plan(self, pl, with_mask=False):
-        """Replays the nine masked layers of a plan whose stage A has run (`head.forward`) into
-        the tape -- the same mask bits and `exact_mask_order` handling as
-        `HeadGrad.forward_from_plan` -- then tapes the heads of all layer outputs."""
+    def _replay_layers(self, pl, keep=None):
+        """The nine masked layers of a plan whose stage A has run, into the tape (`self.dt`): the
+        same mask bits and `exact_mask_order` handling as `HeadGrad.forward_from_plan`.
+        `keep(i, x)` sees every layer's output (before post_norm)."""
         head, w, E = self.head, self.head.w, self._E
         B, Q, L = pl.B, self.Q, head.num_dec_layers
         full = head.exact_mask_order == "full"
@@ -125,7 +128,6 @@ class SegmenterHeadGrad(HeadGrad):
             head._head_embed(pl.q0, pl, False, True, mp_out=mp)
         scr = E(max([hip.attn_scratch_floats(B, Q, n) for n in pl.N] +
                     [hip.attn_scratch_floats(B, Q, Q)]))
-        q_all = E(L * B * Q, 256)
         layers = []
         for i in range(L):
             l = i % 3
@@ -137,10 +139,20 @@ class SegmenterHeadGrad(HeadGrad):
                                    B, Q, pl.N[l], head.dec_ffn, scr, bits, rowall)
             s["level"] = l
             layers.append(s)
-            q_all[i * B * Q:(i + 1) * B * Q].copy_(x)
+            if keep is not None:
+                keep(i, x)
             if i + 1 < L:                        # post_norm + mask_embed -> the next layer's mask
                 head._head_embed(x, pl, False, full, mp_out=mp)
         self.dt = dict(layers=layers, pl=pl, q_out=x)
+
+    @torch.no_grad()
+    @hip.on_device
+    def forward_from_plan(self, pl, with_mask=False):
+        """Replays the nine masked layers of a plan whose stage A has run (`head.forward`) into
+        the tape (`_replay_layers`), then tapes the heads of all layer outputs."""
+        B, Q, L = pl.B, self.Q, self.head.num_dec_layers
+        q_all = self._E(L * B * Q, 256)
+        self._replay_layers(pl, lambda i, x: q_all[i * B * Q:(i + 1) * B * Q].copy_(x))
         return self.forward(q_all, with_mask)
 
     # ------------------------------------------------------------------ backward
@@ -181,6 +193,53 @@ class SegmenterHeadGrad(HeadGrad):
             raise ValueError("counts %s do not match %d images, %d queries and %d = L * sum rows"
                              % (counts, B, Q, M))
         return g_cls.contiguous(), g_mask.contiguous(), rows.contiguous(), counts
+
+    def _layers_bwd(self, dx, dqpos_rows, dmem, grads_out, ready, deep=None):
+        """The walk through the nine masked layers, last to first: `dx` [B * Q, 256] enters the last
+        layer's output; `deep` [L, B * Q, 256] (deep supervision) is the gradient each earlier
+        layer's output receives from its own heads, added in after the layer above it, None for a
+        head without it.  Adds into `dmem`, `dqpos_rows`, `level_embed` and the layers' gradients;
+        -> the gradient into the initial queries."""
+        head, w, E = self.head, self.head.w, self._E
+        pl, layers = self.dt["pl"], self.dt["layers"]
+        B, Q, L = pl.B, self.Q, head.num_dec_layers
+        mk = self.masked_keysplit_min_keys
+        ks_levels = [n for n in pl.N if mk is not None and n >= mk]
+        scr = E(max([hip.mha_bwd_scratch_floats(B, Q, n) for n in pl.N if n not in ks_levels] +
+                    [hip.mha_bwd_scratch_floats(B, Q, Q)]))
+        ks_scr = E(max(hip.mha_bwd_keysplit_scratch_floats(B, Q, n) for n in ks_levels)) \
+            if ks_levels else None                       # (allocated only when a layer uses it)
+        le, dle = w["level_embed.weight"], grads_out["level_embed.weight"]
+        for i in reversed(range(L)):
+            pre = "transformer_decoder.layers.%d." % i
+            ac = pre + "attentions.0.attn."
+            Wc = w[ac + "in_proj_weight"]
+            s = layers[i]
+            l, Nk = s["level"], pl.N[s["level"]]
+            if mk is not None and Nk >= mk:
+                dx, dK, dV = self._layer_bwd(pre, s, dx, grads_out, B, Q, Nk, scr, dqpos_rows,
+                                             True, ks_scr)
+            else:
+                dx, dK, dV = self._layer_bwd(pre, s, dx, grads_out, B, Q, Nk, scr, dqpos_rows)
+            if i > 0 and deep is not None:       # deep supervision: layer i - 1's output has heads
+                self._acc(dx, deep[i - 1])
+            # K = (mem_l + level_embed_l + pe_l) Wk^T + bk, V = (mem_l + level_embed_l) Wv^T + bv
+            # (pairnet_head.py:278-287, :302-312), image by image, as HeadGrad.backward
+            for b in range(B):
+                mem = pl.X[b, pl.start[l]:pl.start[l] + Nk]
+                memk, memv = E(Nk, 256), E(Nk, 256)
+                hip.add_periodic(mem, pl.dec_kpos[l], memk)
+                hip.add_periodic(mem, le[l:l + 1], memv)
+                dmk = self._lin_bwd(dK[b * Nk:(b + 1) * Nk], memk, Wc[256:512], grads_out,
+                                    ac + "in_proj_weight", ac + "in_proj_bias", row0=256)
+                dmv = self._lin_bwd(dV[b * Nk:(b + 1) * Nk], memv, Wc[512:], grads_out,
+                                    ac + "in_proj_weight", ac + "in_proj_bias", row0=512)
+                self._acc(dmk, dmv)
+                dm = dmem[b, pl.start[l]:pl.start[l] + Nk]
+                self._acc(dm, dmk)
+                hip.colsum(dmk, dle[l], accumulate=True)      # level_embed_l feeds K and V
+            ready(self.group_end["transformer_decoder.layers.%d" % i])
+        return dx
 
     @torch.no_grad()
     @hip.on_device
@@ -241,45 +300,10 @@ class SegmenterHeadGrad(HeadGrad):
         # ---- the nine layers, last to first, each layer's own head gradient added in ----
         dmem = zeros(B, pl.SN, 256) if seed_dmem is None else seed_dmem
         dqpos_rows = zeros(B * Q, 256)
-        mk = self.masked_keysplit_min_keys
-        ks_levels = [n for n in pl.N if mk is not None and n >= mk]
-        scr = E(max([hip.mha_bwd_scratch_floats(B, Q, n) for n in pl.N if n not in ks_levels] +
-                    [hip.mha_bwd_scratch_floats(B, Q, Q)]))
-        ks_scr = E(max(hip.mha_bwd_keysplit_scratch_floats(B, Q, n) for n in ks_levels)) \
-            if ks_levels else None                       # (allocated only when a layer uses it)
-        le, dle = w["level_embed.weight"], grads_out["level_embed.weight"]
         dx = self.dq_all[L - 1].clone()
         if seed_dq is not None:
             self._acc(dx, seed_dq)
-        for i in reversed(range(L)):
-            pre = "transformer_decoder.layers.%d." % i
-            ac = pre + "attentions.0.attn."
-            Wc = w[ac + "in_proj_weight"]
-            s = layers[i]
-            l, Nk = s["level"], pl.N[s["level"]]
-            if mk is not None and Nk >= mk:
-                dx, dK, dV = self._layer_bwd(pre, s, dx, grads_out, B, Q, Nk, scr, dqpos_rows,
-                                             True, ks_scr)
-            else:
-                dx, dK, dV = self._layer_bwd(pre, s, dx, grads_out, B, Q, Nk, scr, dqpos_rows)
-            if i > 0:                            # deep supervision: layer i - 1's output has heads
-                self._acc(dx, self.dq_all[i - 1])
-            # K = (mem_l + level_embed_l + pe_l) Wk^T + bk, V = (mem_l + level_embed_l) Wv^T + bv
-            # (pairnet_head.py:278-287, :302-312), image by image, as HeadGrad.backward
-            for b in range(B):
-                mem = pl.X[b, pl.start[l]:pl.start[l] + Nk]
-                memk, memv = E(Nk, 256), E(Nk, 256)
-                hip.add_periodic(mem, pl.dec_kpos[l], memk)
-                hip.add_periodic(mem, le[l:l + 1], memv)
-                dmk = self._lin_bwd(dK[b * Nk:(b + 1) * Nk], memk, Wc[256:512], grads_out,
-                                    ac + "in_proj_weight", ac + "in_proj_bias", row0=256)
-                dmv = self._lin_bwd(dV[b * Nk:(b + 1) * Nk], memv, Wc[512:], grads_out,
-                                    ac + "in_proj_weight", ac + "in_proj_bias", row0=512)
-                self._acc(dmk, dmv)
-                dm = dmem[b, pl.start[l]:pl.start[l] + Nk]
-                self._acc(dm, dmk)
-                hip.colsum(dmk, dle[l], accumulate=True)      # level_embed_l feeds K and V
-            ready(self.group_end["transformer_decoder.layers.%d" % i])
+        dx = self._layers_bwd(dx, dqpos_rows, dmem, grads_out, ready, self.dq_all)
         hip.batch_sum(dx, grads_out["query_feat.weight"], B)
         hip.batch_sum(dqpos_rows, grads_out["query_embed.weight"], B)
         ready(self.group_end["query"])
@@ -527,6 +551,181 @@ class BaselineHeadGrad(SegmenterHeadGrad):
                                               seed_dmem=dmem)
         finally:
             self._zeroed = False
+
+
+class PSGTr2HeadGrad(SegmenterHeadGrad):
+    """The tape of `PSGTrHead2` ("PSGTR on Mask2Former", psgtr_head2.py:288-444): from the six
+    entries `PSGTrHead2.triplet_losses(..., grads={})` fills to every head parameter the reference's
+    `losses.backward()` reaches behind the pixel decoder (179 tensors), dmem and dMF:
+
+        tape = PSGTr2HeadGrad(head); head.forward(feats, metas)
+        out = tape.forward_from_plan(head._last_plan)       # sub, obj, rel, me (, sub_seg, obj_seg)
+        losses = head.triplet_losses(..., grads=g)
+        dmem, dMF, grads = tape.backward(g, counts=head._tri_loss.last["counts"])
+
+    What differs from the parent: no deep supervision -- only the last layer's output carries loss
+    terms -- and ONE head chain over q_all [2 * B * Q, 256].  Rows 0 .. B * Q - 1 are the last
+    layer's output (the three class heads and, sic, `obj_mask_embed` -> the returned `sub_seg`);
+    rows B * Q .. 2 * B * Q - 1 are the batch-repeated `query_feat` (`obj_mask_embed` -> the stale
+    `obj_seg` of the initial forward_head call; module docstring of psgtr_head2.py).  `post_norm` and
+    `obj_mask_embed` run on all rows, the class heads on the first half; the two mask products are
+    the parent's kernels with L = 2 (subject rows, then object rows shifted by B * Q); the three
+    ragged class heads go back in the two launches of `pn_triplet_heads_bwd_f32`
+    (csrc/tri_grad.hip).  The second half's gradient lands in `query_feat`'s batch sum.
+
+    `mask_embed.*` and `sub_mask_embed.*` are not in the layout: the first feeds only the detached
+    attention masks, the second reaches no output -- autograd leaves both at `grad is None`."""
+
+    KEYS = ("sub", "obj", "rel", "mask_rows", "sub_mask", "obj_mask")
+
+    @staticmethod
+    def param_groups(head):
+        heads = ["%s_cls_embed.%s" % (h, n) for h in ("sub", "obj", "rel") for n in ("weight", "bias")]
+        heads += ["obj_mask_embed.%d.%s" % (j, n) for j in (4, 2, 0) for n in ("weight", "bias")]
+        heads += ["transformer_decoder.post_norm.weight", "transformer_decoder.post_norm.bias"]
+        return [("heads", heads)] + SegmenterHeadGrad.param_groups(head)[1:]
+
+    # ------------------------------------------------------------------ forward with a tape
+    @torch.no_grad()
+    @hip.on_device
+    def forward_from_plan(self, pl, with_mask=False):
+        """Replays the nine masked layers (the attention masks still come from the untrained
+        `mask_embed` through `head._head_embed`), then tapes the one head chain.  -> dict(sub, obj
+        [1, B, Q, C + 1], rel [1, B, Q, Cr + 1], me [2 * B * Q, 256] and, with `with_mask`, sub_seg /
+        obj_seg [1, B, Q, H2, W2]) in buffers of the tape's own."""
+        head, w, E = self.head, self.head.w, self._E
+        self.st = None
+        self._replay_layers(pl)
+        B, Q = pl.B, self.Q
+        N = B * Q
+        q_all = E(2 * N, 256)
+        q_all[:N].copy_(self.dt["q_out"])
+        q_all[N:].copy_(pl.q0)
+        qn, m1, m2, me = E(2 * N, 256), E(2 * N, 256), E(2 * N, 256), E(2 * N, 256)
+        hip.layernorm(q_all, w["transformer_decoder.post_norm.weight"],
+                      w["transformer_decoder.post_norm.bias"], qn)
+        out = {}
+        for key, name in (("sub", "sub_cls_embed"), ("obj", "obj_cls_embed"), ("rel", "rel_cls_embed")):
+            n = w[name + ".weight"].shape[0]
+            out[key] = E(1, B, Q, n)
+            hip.linear(qn[:N], w[name + ".weight"], w[name + ".bias"], out[key].view(N, n))
+        hip.linear(qn, w["obj_mask_embed.0.weight"], w["obj_mask_embed.0.bias"], m1, relu=True)
+        hip.linear(m1, w["obj_mask_embed.2.weight"], w["obj_mask_embed.2.bias"], m2, relu=True)
+        hip.linear(m2, w["obj_mask_embed.4.weight"], w["obj_mask_embed.4.bias"], me)
+        self.st = dict(q=q_all, qn=qn, mlp=(m1, m2, me), B=B, L=2)
+        out["me"] = me
+        if with_mask:
+            H2, W2 = pl.hw2
+            for key, rows in (("sub_seg", me[:N]), ("obj_seg", me[N:])):
+                out[key] = E(1, B, Q, H2, W2)
+                head._mask_logits(rows, pl, out[key].view(B, Q, pl.HW2))
+        return out
+
+    # ------------------------------------------------------------------ backward
+    def _check_tri_grads(self, grads, counts):
+        st, pl = self.st, self.dt["pl"]
+        B, Q = st["B"], self.Q
+        w = self.head.w
+        if not isinstance(grads, dict):
+            raise ValueError("grads: the dict `triplet_losses(..., grads={})` fills")
+        unknown = sorted(set(grads) - set(self.KEYS))
+        if unknown:
+            raise ValueError("grads has unknown keys %s" % unknown)
+        for k in self.KEYS:
+            if k not in grads:
+                raise ValueError("grads lacks %r (PSGTrHead2.triplet_losses(..., grads={}))" % k)
+            t = grads[k]
+            dt = torch.int64 if k == "mask_rows" else torch.float32
+            if not (torch.is_tensor(t) and t.is_cuda and t.device == self.dev and t.dtype == dt):
+                raise ValueError("grads[%r]: a %s tensor on %s" % (k, dt, self.dev))
+        for k, name in (("sub", "sub_cls_embed"), ("obj", "obj_cls_embed"), ("rel", "rel_cls_embed")):
+            shape = (1, B, Q, w[name + ".weight"].shape[0])
+            if tuple(grads[k].shape) != shape:
+                raise ValueError("grads[%r] %s does not match the tape's %s"
+                                 % (k, tuple(grads[k].shape), shape))
+        rows = grads["mask_rows"]
+        M = int(rows.shape[0])
+        for k in ("sub_mask", "obj_mask"):
+            g = grads[k]
+            if rows.dim() != 1 or g.dim() != 3 or g.shape[0] != M or \
+                    (M and tuple(g.shape[1:]) != tuple(pl.hw2)):
+                raise ValueError("grads[%r] %s / ['mask_rows'] %s do not match the tape's [M, %d, %d]"
+                                 % (k, tuple(g.shape), tuple(rows.shape), pl.hw2[0], pl.hw2[1]))
+        if counts is None:
+            if B != 1:
+                raise ValueError("counts: the matched rows per image (min(Q, R_b)), needed for B > 1")
+            counts = [M]
+        counts = [int(c) for c in counts]
+        if len(counts) != B or min(counts) < 0 or max(counts) > Q or sum(counts) != M:
+            raise ValueError("counts %s do not match %d images, %d queries and %d rows"
+                             % (counts, B, Q, M))
+        return counts
+
+    @torch.no_grad()
+    @hip.on_device
+    def backward(self, grads, counts=None, on_ready=None):
+        """`grads`: "sub", "obj" [1, B, Q, C + 1], "rel" [1, B, Q, Cr + 1], "mask_rows" [M] (rows in
+        [0, B * Q), -1 for a failed image) and "sub_mask" / "obj_mask" [M, H2, W2] as
+        `PSGTrHead2Loss.loss(..., grads={})` fills them; `counts`: the matched rows per image (the
+        loss object's `last["counts"]`; optional for one image).  Nothing is read back from the
+        device.  -> (dmem [B, SN, 256], dMF [B, H2 * W2, 256], {reference parameter name:
+        gradient}), the gradients views of `self.flat_grad`; `on_ready(end)` as the parent."""
+        if self.st is None:
+            raise RuntimeError("backward() needs a forward_from_plan() first")
+        counts = self._check_tri_grads(grads, counts)
+        mk = self.masked_keysplit_min_keys
+        if mk is not None and (isinstance(mk, bool) or not isinstance(mk, int) or mk < 0):
+            raise ValueError("masked_keysplit_min_keys %r: None or an integer >= 0" % (mk,))
+        w, E, st = self.head.w, self._E, self.st
+        pl = self.dt["pl"]
+        B, Q = st["B"], self.Q
+        N, P = B * Q, pl.HW2
+        rows = grads["mask_rows"].contiguous()
+        M = int(rows.shape[0])
+        ready = on_ready if on_ready is not None else (lambda end: None)
+        zeros = lambda *s_: torch.zeros(*s_, device=self.dev, dtype=torch.float32)
+        g = self._zero_grads()
+        me = st["mlp"][2]
+        # ---- the two mask products with L = 2: subject rows, then object rows B * Q further on ----
+        table, T = self._table(2, counts)
+        gs, go = grads["sub_mask"].contiguous(), grads["obj_mask"].contiguous()
+        if M and go.data_ptr() == gs.data_ptr() + 4 * M * P and \
+                gs.untyped_storage().data_ptr() == go.untyped_storage().data_ptr():
+            G = torch.as_strided(gs, (2 * M, P), (P, 1))          # the two halves of ONE buffer
+        else:
+            G = torch.cat([gs.view(M, P), go.view(M, P)])
+        rows2 = torch.cat([rows, torch.where(rows >= 0, rows + N, rows)])
+        dMF = E(B, P, 256)
+        hip.mask_feature_grad(G, me, rows2, table, T, dMF)
+        if M:
+            dme = E(2 * M, 256)
+            hip.mask_embed_grad(G, pl.MF.view(B, P, 256), rows2, table, T, dme,
+                                E(hip.mask_embed_grad_scratch_floats(T, P)))
+            dme_all = E(2 * N, 256)             # (a matched row appears once; failed rows match none)
+            hip.scatter_rows_add(dme, rows2, dme_all, 1, 2 * N, 2 * M, 256)
+        else:
+            dme_all = zeros(2 * N, 256)
+        # ---- obj_mask_embed on all rows, the three class heads on the first half, post_norm ----
+        dqn = self._mlp3_bwd(dme_all, st["qn"], st["mlp"], "obj_mask_embed", g)
+        hip.tri_heads_bwd(
+            grads["sub"].contiguous().view(N, -1), grads["obj"].contiguous().view(N, -1),
+            grads["rel"].contiguous().view(N, -1), st["qn"][:N], w["sub_cls_embed.weight"],
+            w["obj_cls_embed.weight"], w["rel_cls_embed.weight"], dqn[:N],
+            g["sub_cls_embed.weight"], g["sub_cls_embed.bias"], g["obj_cls_embed.weight"],
+            g["obj_cls_embed.bias"], g["rel_cls_embed.weight"], g["rel_cls_embed.bias"], add=True)
+        dq_all = self._ln_bwd(dqn, st["q"], "transformer_decoder.post_norm.", g)
+        self.dq_all = dq_all.view(2, N, 256)
+        ready(self.group_end["heads"])
+        # ---- the nine layers, last to first, from the first half; no deep supervision ----
+        dmem = zeros(B, pl.SN, 256)
+        dqpos_rows = zeros(N, 256)
+        dx = self._layers_bwd(self.dq_all[0].clone(), dqpos_rows, dmem, g, ready)
+        hip.batch_sum(dx, g["query_feat.weight"], B)
+        hip.batch_sum(self.dq_all[1], g["query_feat.weight"], B, accumulate=True)   # the stale masks
+        hip.batch_sum(dqpos_rows, g["query_embed.weight"], B)
+        ready(self.group_end["query"])
+        ready(self.flat_numel)
+        return dmem, dMF, g
 
 
 class SegPixelDecoderGrad(PixelDecoderGrad):
