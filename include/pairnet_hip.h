@@ -174,6 +174,23 @@ int pn_bottleneck_proj_f32(const float* x, const float* Wsc, const float* bsc, c
                            int H, int W, int Cin, int planes, int Cout, int stride, int flags,
                            float* splitk_scratch /* or NULL */, int64_t splitk_scratch_floats,
                            void* stream);
+/* Grouped 3x3 convolution, pad 1 (zeros outside the image), stride 1 or 2, channel-last: conv2 of
+ * the ResNeXt bottlenecks.  The reference reaches it through mmdet's ResNeXt, configured at
+ * configs/deformable_detr/pairnet_rnext101_vg.py:9-21 (type "ResNeXt", groups 32, base_width 8);
+ * mmdet is third-party and its layer is restated from memory, unpinned.
+ *   out[b][oy][ox][g*Cg + co] = act(sum_{ky,kx,ci} in[b][oy*s+ky-1][ox*s+kx-1][g*Cg + ci]
+ *                                   * Wg[g][co][(ky*3+kx)*Cg + ci] + bias[g*Cg + co])
+ * in [B][H][W][G*Cg], out [B][Ho][Wo][G*Cg], Ho = (H - 1) / stride + 1 (same for W); Wg
+ * [G][Cg][9*Cg] is the PyTorch weight [G*Cg][Cg][3][3] with each row reordered to (ky, kx, ci).
+ * Cg in {8, 16, 32, 64}, any G >= 1; KH = KW = 3; stride 1 or 2; flags: 0 or PN_GEMM_RELU; `in`
+ * and `Wg` 16-byte aligned; B*H*W*G*Cg < 2^31 (the kernel indexes with int32).  Anything else is
+ * PN_BAD_ARG before a launch.  Every output is ONE fixed-order fp32 MFMA chain of 9*Cg products
+ * followed by the bias: no atomics, no split, bitwise reproducible.  At Cg = 8 two neighbouring
+ * groups share a 16-channel MFMA tile with a block-diagonal weight operand: the other group's
+ * inputs meet exact zeros, so a non-finite input there turns this group's outputs into NaN. */
+int pn_conv2d_grouped_nhwc_f32(const float* in, const float* Wg, const float* bias, float* out,
+                               int B, int H, int W, int G, int Cg, int KH, int KW, int stride,
+                               int flags, void* stream);
 /* Stem: relu(conv7x7/2 pad 3 (NCHW RGB image) + bias) -> [B][Ho][Wo][64] channel-last.
  * Wp [64][160] = conv1.weight [64][3][7][7] flattened, zero-padded 147 -> 160. */
 int pn_stem7x7s2_f32(const float* img_nchw, const float* Wp, const float* bias,

@@ -1,11 +1,11 @@
 """Public names of the package (what a user of the reference looks for)."""
 from .config import (ConfigDict, baseline_head_cfg, baseline_r50, bbox_head_cfg,  # noqa: F401
-                     channel_mapper_cfg, cross_r101_vg, load_config,
+                     channel_mapper_cfg, cross_r101_vg, load_config, pairnet_rnext101_vg,
                      pairnet_head_cfg, pairnet_r50, pairnet_swin, psgtr2_head_cfg, psgtr2_r50,
                      psgtr2_train_cfg,
                      swin_backbone_cfg, test_pipeline_cfg, train_pipeline_cfg)
 from .psgtr_head2 import PSGTrHead2  # noqa: F401
-from .backbone import ResNet50Hip  # noqa: F401
+from .backbone import ResNet50Hip, ResNeXtHip  # noqa: F401
 from .swin import SwinTransformerHip  # noqa: F401
 from .baseline_head import CrossHeadBaseline  # noqa: F401
 from .bbox_head import CrossHeadBBox  # noqa: F401
@@ -42,4 +42,5 @@ __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "Cros
            "TripletEvaluator", "SceneGraphMetrics", "StreamingEvaluator", "PanopticQuality", "dataset", "RelationTailGrad", "HeadGrad", "PixelDecoderGrad", "BackboneGrad", "SwinBackboneGrad", "SwinStagesGrad", "SegmenterHeadGrad", "BaselineHeadGrad", "SegPixelDecoderGrad", "TailTrainer", "BaselineTrainer", "FfnDropout",
            "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg", "Mask2FormerLoss",
            "BaselineRelationLoss", "BBoxTailGrad", "BBoxTrainer", "CrossHeadBBoxLoss",
-           "PSGTrHead2Loss", "psgtr2_train_cfg", "PSGTr2HeadGrad", "PSGTr2Trainer"]
+           "PSGTrHead2Loss", "psgtr2_train_cfg", "PSGTr2HeadGrad", "PSGTr2Trainer",
+           "ResNeXtHip", "pairnet_rnext101_vg"]

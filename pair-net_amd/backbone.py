@@ -28,7 +28,13 @@ def _stages(depth):
     return tuple(zip((64, 128, 256, 512), BLOCKS[depth]))
 
 
-def _param_shapes(depth=50):
+def _width(planes, groups=1, base_width=64):
+    """mmdet's bottleneck width: `planes` for a ResNet, floor(planes * base_width / 64) * groups
+    for a ResNeXt (32x8d: 256 / 512 / 1024 / 2048)."""
+    return planes if groups == 1 else (planes * base_width // 64) * groups
+
+
+def _param_shapes(depth=50, groups=1, base_width=64):
     STAGES = _stages(depth)
     s = OrderedDict()
 
@@ -43,11 +49,12 @@ def _param_shapes(depth=50):
     for i, (planes, blocks) in enumerate(STAGES):
         for b in range(blocks):
             p = "layer%d.%d." % (i + 1, b)
-            s[p + "conv1.weight"] = (planes, cin, 1, 1)
-            bn(p + "bn1", planes)
-            s[p + "conv2.weight"] = (planes, planes, 3, 3)
-            bn(p + "bn2", planes)
-            s[p + "conv3.weight"] = (planes * 4, planes, 1, 1)
+            width = _width(planes, groups, base_width)
+            s[p + "conv1.weight"] = (width, cin, 1, 1)
+            bn(p + "bn1", width)
+            s[p + "conv2.weight"] = (width, width // groups, 3, 3)
+            bn(p + "bn2", width)
+            s[p + "conv3.weight"] = (planes * 4, width, 1, 1)
             bn(p + "bn3", planes * 4)
             if b == 0:
                 s[p + "downsample.0.weight"] = (planes * 4, cin, 1, 1)
@@ -60,12 +67,18 @@ class ResNet50Hip:
     """Drop-in for the detector's `backbone(img) -> (C2, C3, C4, C5)`."""
 
     def __init__(self, depth=50, **unused):
+        self._init(depth)
+
+    def _init(self, depth, groups=1, base_width=64):
         if depth not in BLOCKS:
             raise NotImplementedError("bottleneck ResNets: depth 50 or 101")
         self.depth, self.stages = depth, _stages(depth)
+        # conv2's groups and the bottleneck width of each stage (= planes for a ResNet)
+        self.groups = groups
+        self.widths = tuple(_width(planes, groups, base_width) for planes, _ in self.stages)
         self._params = OrderedDict(
             (k, torch.zeros(shape, dtype=torch.int64 if k.endswith("tracked") else torch.float32))
-            for k, shape in _param_shapes(depth).items())
+            for k, shape in _param_shapes(depth, groups, base_width).items())
         for k, v in self._params.items():          # identity BatchNorm until weights are loaded
             if k.endswith(("running_var",)) or (k.endswith(".weight") and v.dim() == 1):
                 v.fill_(1.0)
@@ -173,7 +186,8 @@ class ResNet50Hip:
                     # stride-1 3x3 layers of >= 128 channels also get their Winograd F(2x2,3x3)
                     # weights (stages 2-4; the 64-channel layers of stage 1 would be K = 64
                     # GEMMs, slower than the direct form)
-                    if conv == "conv2" and co >= 64 and not (b == 0 and i > 0):
+                    if conv == "conv2" and co >= 64 and not (b == 0 and i > 0) \
+                            and self.groups == 1:
                         w[p + "conv2.wino"] = hip.winograd_weights(cw.to(dev))
                         w[p + "conv2.wino4"] = hip.winograd43_weights(cw.to(dev))
         # conv3 (BN folded) as S3 operands for the bf16-pipe GEMM, split once
@@ -268,12 +282,13 @@ class ResNet50Hip:
             if i > 0:
                 h, wd = (h - 1) // 2 + 1, (wd - 1) // 2 + 1
             pl.hw.append(((hin, win), (h, wd)))
-            pl.t1.append(E(B, hin, win, planes))       # conv1 output at the input resolution
-            pl.t2.append(E(B, h, wd, planes))
+            width = self.widths[i]
+            pl.t1.append(E(B, hin, win, width))        # conv1 output at the input resolution
+            pl.t2.append(E(B, h, wd, width))
             pl.idt.append(E(B, h, wd, planes * 4))
             pl.ping.append(E(B, h, wd, planes * 4))
             pl.out.append(E(B, h, wd, planes * 4))
-            if planes >= self.wino_min_planes:
+            if planes >= self.wino_min_planes and self.groups == 1:
                 t2, t4 = B * ((h + 1) // 2) * ((wd + 1) // 2), B * ((h + 3) // 4) * ((wd + 3) // 4)
                 nwino = max(nwino, 16 * t2 * planes, 36 * t4 * planes)
                 # F(4x4,3x3) where it multiplies fewer (64-row padded) GEMM rows
@@ -282,8 +297,8 @@ class ResNet50Hip:
                 pl.f43.append(False)
         pl.wV, pl.wM = E(max(nwino, 4)), E(max(nwino, 4))   # Winograd transform planes
         # the 3x3 convolution's output once more as an S3 operand (conv3's A, s3_conv3_min_planes)
-        pl.t2_s3 = E(max(hip.s3_floats(B * hw[1][0] * hw[1][1], planes)
-                         for hw, (planes, _) in zip(pl.hw, self.stages)))
+        pl.t2_s3 = E(max(hip.s3_floats(B * hw[1][0] * hw[1][1], width)
+                         for hw, width in zip(pl.hw, self.widths)))
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
@@ -356,18 +371,24 @@ class ResNet50Hip:
         x, cin = pl.pool, 64
         for i, (planes, blocks) in enumerate(self.stages):
             (hin, win), (h, wd) = pl.hw[i]
+            width = self.widths[i]            # bottleneck width (= planes for a ResNet)
             for b in range(blocks):
                 p = "layer%d.%d." % (i + 1, b)
                 stride = 2 if (b == 0 and i > 0) else 1
                 hi, wi = (hin, win) if b == 0 else (h, wd)
-                t1 = pl.t1[i].view(-1)[:B * hi * wi * planes].view(B, hi, wi, planes)
+                t1 = pl.t1[i].view(-1)[:B * hi * wi * width].view(B, hi, wi, width)
                 # conv1 1x1 (+BN+ReLU): a GEMM over the pixels
                 hip.linear(x.view(-1, cin), w[p + "conv1.w"], w[p + "conv1.b"],
-                           t1.view(-1, planes), relu=True, scratch=pl.scratch)
+                           t1.view(-1, width), relu=True, scratch=pl.scratch)
                 # conv2 3x3, stride on this layer ("pytorch" style) (+BN+ReLU)
                 wino = self.conv_algo in ("winograd", "winograd4") and p + "conv2.wino" in w \
                     and stride == 1 and planes >= self.wino_min_planes
-                if wino and self.conv_algo == "winograd4" and pl.f43[i]:
+                if self.groups > 1:
+                    # ResNeXt: grouped 3x3 (one launch, csrc/grouped_conv.hip); the Winograd
+                    # switches do not apply
+                    hip.conv3x3_grouped(t1, w[p + "conv2.w"], w[p + "conv2.b"], pl.t2[i], B, hi,
+                                        wi, self.groups, width // self.groups, stride, relu=True)
+                elif wino and self.conv_algo == "winograd4" and pl.f43[i]:
                     # 4x fewer multiplications (fp32; ~1.6e-5 relative to the direct form)
                     hip.conv3x3_winograd43(t1, w[p + "conv2.wino4"], w[p + "conv2.b"], pl.t2[i],
                                            pl.wV, pl.wM, B, hi, wi, planes, planes, True)
@@ -387,7 +408,7 @@ class ResNet50Hip:
                     dst = pl.out[i] if blocks == 1 else pl.ping[i]
                     hip.bottleneck_proj(x, w[p + "downsample.0.w"], w[p + "downsample.0.b"],
                                         pl.t2[i], w[p + "conv3.w"], w[p + "conv3.b"], pl.idt[i],
-                                        dst, B, hi, wi, cin, planes, stride, scratch=pl.scratch)
+                                        dst, B, hi, wi, cin, width, stride, scratch=pl.scratch)
                     x, cin = dst, planes * 4
                     continue
                 # shortcut: projection in the first block of a stage, identity after it
@@ -409,16 +430,50 @@ class ResNet50Hip:
                 else:
                     dst = pl.ping[i] if idt is not pl.ping[i] else pl.idt[i]
                 if s3:
-                    t2 = pl.t2[i].view(-1, planes)
+                    t2 = pl.t2[i].view(-1, width)
                     hip.s3_split(t2, pl.t2_s3)
-                    hip.gemm_s3(pl.t2_s3, w[p + "conv3.w.s3"], t2.shape[0], planes * 4, planes,
+                    hip.gemm_s3(pl.t2_s3, w[p + "conv3.w.s3"], t2.shape[0], planes * 4, width,
                                 bias=w[p + "conv3.b"], out=dst.view(-1, planes * 4),
                                 res=idt.view(-1, planes * 4), relu_after=True)
                 else:
-                    hip.linear(pl.t2[i].view(-1, planes), w[p + "conv3.w"], w[p + "conv3.b"],
+                    hip.linear(pl.t2[i].view(-1, width), w[p + "conv3.w"], w[p + "conv3.b"],
                                dst.view(-1, planes * 4), res=idt.view(-1, planes * 4),
                                relu_after=True, scratch=pl.scratch)
                 x, cin = dst, planes * 4
         return tuple(o.permute(0, 3, 1, 2) for o in pl.out)
 
     __call__ = forward
+
+
+GROUP_WIDTHS = (8, 16, 32, 64)      # channels per group pn_conv2d_grouped_nhwc_f32 is built for
+# mmdet ResNet / ResNeXt keys that change nothing in a frozen-BatchNorm, forward-only backbone
+_IGNORED_KEYS = ("num_stages", "out_indices", "frozen_stages", "norm_cfg", "norm_eval", "style",
+                 "with_cp", "init_cfg", "pretrained")
+
+
+class ResNeXtHip(ResNet50Hip):
+    """mmdet's ResNeXt (configs/deformable_detr/pairnet_rnext101_vg.py:9-21: depth 101, groups 32,
+    base_width 8; third party, restated from memory, unpinned): the bottleneck ResNet with
+    conv1 cin -> width, conv2 a GROUPED 3x3 width -> width (stride on it, "pytorch" style) and
+    conv3 width -> 4 planes, width = floor(planes * base_width / 64) * groups.  State-dict names
+    and shapes are mmdet's / torchvision's (`layerN.M.conv2.weight` is [width, width / groups, 3,
+    3]).  Forward only: there is no grouped-convolution backward.  `with_cp` (activation
+    checkpointing, a training-memory option) is accepted and ignored."""
+
+    def __init__(self, depth=101, groups=32, base_width=8, **cfg):
+        unknown = sorted(k for k in cfg if k not in _IGNORED_KEYS)
+        if unknown:
+            raise NotImplementedError("ResNeXtHip: unknown keys %s" % unknown)
+        if cfg.get("num_stages", 4) != 4 or cfg.get("style", "pytorch") != "pytorch":
+            raise NotImplementedError("ResNeXtHip: four stages, style 'pytorch'")
+        if depth not in BLOCKS:
+            raise NotImplementedError("bottleneck ResNeXts: depth 50 or 101")
+        per_group = [planes * base_width // 64 for planes, _ in _stages(depth)]
+        if groups < 2 or any(c not in GROUP_WIDTHS for c in per_group):
+            raise NotImplementedError(
+                "ResNeXtHip: groups=%d, base_width=%d gives %s channels per group; the grouped "
+                "convolution is built for %s (32x8d)" % (groups, base_width, per_group,
+                                                         list(GROUP_WIDTHS)))
+        self.base_width = base_width
+        self._init(depth, groups, base_width)
+        self.conv_algo = "direct"       # (a grouped layer has no Winograd form)

@@ -281,6 +281,17 @@ def cross_r101_vg():
         neck=channel_mapper_cfg(), bbox_head=bbox_head_cfg(), test_cfg=dict(max_per_img=100)))
 
 
+def pairnet_rnext101_vg():
+    """configs/deformable_detr/pairnet_rnext101_vg.py:7-117: the same detector on ResNeXt-101
+    32x8d (the `model` section differs from cross_r101_vg.py in `backbone` only)."""
+    cfg = cross_r101_vg()
+    cfg.model["backbone"] = _to_cfg(dict(
+        type="ResNeXt", depth=101, groups=32, base_width=8, num_stages=4, out_indices=(1, 2, 3),
+        frozen_stages=1, norm_cfg=dict(type="BN", requires_grad=False), norm_eval=True,
+        style="pytorch", with_cp=True))
+    return cfg
+
+
 def test_pipeline_cfg():
     """`test_pipeline` of configs/mask2former/pairnet.py:310-331 (what preprocess.TestPipeline
     .from_config consumes)."""

@@ -19,7 +19,7 @@ import torch
 
 from . import hip
 from .config import ConfigDict
-from .backbone import ResNet50Hip
+from .backbone import ResNet50Hip, ResNeXtHip
 from .baseline_head import CrossHeadBaseline
 from .bbox_head import CrossHeadBBox
 from .head import CrossHead2
@@ -405,9 +405,14 @@ class PSGTr:
             # the native fp32-MFMA backbone of backbone.py, channels_last features straight
             # into the head
             self.backbone = ResNet50Hip(depth=backbone.get("depth", 50))
+        elif btype == "ResNeXt" and backbone.get("depth", 101) in (50, 101):
+            # configs/deformable_detr/pairnet_rnext101_vg.py:9-21 (32x8d): grouped 3x3 layers on
+            # csrc/grouped_conv.hip; forward only
+            self.backbone = ResNeXtHip(**{k: v for k, v in backbone.items() if k != "type"})
         else:
             raise NotImplementedError("backbones built: ResNet depth 50 / 101 (pairnet.py, "
-                                      "psgformer_r101_psg.py) and SwinTransformer "
+                                      "psgformer_r101_psg.py), ResNeXt depth 50 / 101 "
+                                      "(pairnet_rnext101_vg.py) and SwinTransformer "
                                       "(pairnet_swinb.py)")
         head_cfg = dict(bbox_head)
         heads = dict(CrossHead2=CrossHead2, CrossHeadBaseline=CrossHeadBaseline,
@@ -607,6 +612,16 @@ class PSGTr:
                 prepared.append(out)
         return prepared
 
+    def _forward_only_backbone(self, train_backbone):
+        """A ResNeXt backbone has no backward (no grouped-convolution gradient kernels): asking a
+        trainer to tape it raises before anything else happens; left to the default it stays
+        frozen (`train_backbone=False`), although it is a subclass of the trainable ResNet."""
+        if isinstance(self.backbone, ResNeXtHip):
+            if train_backbone:
+                raise NotImplementedError("ResNeXt backbone: forward only")
+            return False
+        return train_backbone
+
     def trainer(self, train_backbone=None, **kw):
         """The per-iteration part of the reference's training (tools/train.py:115-241 with mmcv's
         runner: `forward_train` -> `losses.backward()` -> OptimizerHook(grad_clip) -> AdamW, under
@@ -630,6 +645,7 @@ class PSGTr:
         step; nothing of it lives here, the keywords pass through)."""
         from .backbone import ResNet50Hip
         from .train import TailTrainer
+        train_backbone = self._forward_only_backbone(train_backbone)
         if type(self.bbox_head) is not CrossHead2:
             raise NotImplementedError("training is built for CrossHead2 only")
         if train_backbone is None:
@@ -699,6 +715,7 @@ class PSGTr:
         `train_step()` and `val_losses()` keep refusing this head."""
         from .backbone import ResNet50Hip
         from .baseline_train import BaselineTrainer
+        train_backbone = self._forward_only_backbone(train_backbone)
         if type(self.bbox_head) is not CrossHeadBaseline:
             raise NotImplementedError("full_trainer is built for CrossHeadBaseline only (%s: "
                                       "trainer())" % type(self.bbox_head).__name__)
@@ -753,6 +770,7 @@ class PSGTr:
         `train_step()` and the other heads' `val_*losses()` keep refusing this head."""
         from .backbone import ResNet50Hip
         from .psgtr2_train import PSGTr2Trainer
+        train_backbone = self._forward_only_backbone(train_backbone)
         if type(self.bbox_head) is not PSGTrHead2:
             raise NotImplementedError("triplet_trainer is built for PSGTrHead2 only (%s: trainer() / "
                                       "full_trainer() / box_trainer())"

@@ -1055,6 +1055,8 @@ class BackboneGrad(RelationTailGrad):
     ~1e-5).  Gradients are named like the backbone's state dict (`layer3.4.conv2.weight`)."""
 
     def __init__(self, backbone, flat=None, base=0):
+        if getattr(backbone, "groups", 1) != 1:     # (ResNeXtHip subclasses the ResNet)
+            raise NotImplementedError("ResNeXt backbone: forward only")
         if backbone.device is None or backbone.device.type != "cuda":
             raise RuntimeError("BackboneGrad needs a backbone on an MI355X (.to('cuda:N'))")
         if backbone.w is None:

@@ -265,6 +265,7 @@ _SIGS = {
     "pn_tri_targets": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32,
                                  _i32, _i64] + [_vp] * 7),
     "pn_triplet_heads_bwd_f32": (C.c_int, [_vp] * 14 + [_i32] * 5 + [_vp]),
+    "pn_conv2d_grouped_nhwc_f32": (C.c_int, [_vp] * 4 + [_i32] * 9 + [_vp]),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 34  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
@@ -538,6 +539,20 @@ def conv2d_ex(x, wp, bias, res, out, B, H, W, Cin, Cout, KH, KW, stride, pad, re
                        KH, KW, stride, pad, flags, _ptr(scratch),
                        scratch.numel() if scratch is not None else 0, _stream())),
            "pn_conv2d_nhwc_ex_f32")
+
+
+def conv3x3_grouped(x, wg, bias, out, B, H, W, G, Cg, stride, relu=False, kh=3, kw=3, flags=0):
+    """Grouped 3x3 convolution, pad 1, channel-last (pn_conv2d_grouped_nhwc_f32): x
+    [B,H,W,G*Cg], wg [G,Cg,9*Cg] ((ky, kx, ci) rows), out [B,Ho,Wo,G*Cg].  `kh`, `kw`, `flags`
+    are passed through as they are (the library refuses anything but 3, 3 and PN_GEMM_RELU)."""
+    Ho, Wo = (H - 1) // max(stride, 1) + 1, (W - 1) // max(stride, 1) + 1
+    flops = 2.0 * B * Ho * Wo * G * Cg * kh * kw * Cg
+    nbytes = 4.0 * (B * (H * W + Ho * Wo) * G * Cg + G * Cg * kh * kw * Cg)
+    _check(_launch("k_conv3x3_grouped<%d,%d>" % (Cg, stride), flops, nbytes,
+                   lambda: lib().pn_conv2d_grouped_nhwc_f32(
+                       _ptr(x), _ptr(wg), _ptr(bias), _ptr(out), B, H, W, G, Cg, kh, kw, stride,
+                       (GEMM_RELU if relu else 0) | flags, _stream())),
+           "pn_conv2d_grouped_nhwc_f32")
 
 
 def bottleneck_proj(x, wsc, bsc, t2, w3, b3, idt, out, B, H, W, Cin, planes, stride,
