@@ -780,6 +780,42 @@ int pn_eval_iou_best(const int32_t* inter, const int32_t* area_pred, const int32
                      int P, int n_obj, const int64_t* pred_labels, const int32_t* gt_labels,
                      const int32_t* gt_sub_row, const int32_t* gt_obj_row, int G, uint8_t* valid,
                      double* best, void* stream);
+/* The box form of that statistic (csrc/nogc.hip), `SGObjectIOU.calculate_iou` -> `_compute_iou_bbox`
+ * (sgg_metrics.py:1025-1028, :1133-1178), for `detection_method="bbox"`: per side s (0: the subject
+ * predictions [0, R), 1: the object predictions [R, 2R)) and ground-truth OBJECT o (objects, not
+ * relations).  The reference hard-codes the split at 100; this splits at R, identical at the only
+ * R any config uses.  pred_boxes [2R] rows of ld_pred floats, pred_labels [2R] int64, gt_boxes
+ * [n_obj] rows of ld_gt floats (x1, y1, x2, y2), gt_labels [n_obj] int32.
+ *   valid [2][n_obj] uint8: some prediction of that side has the object's class
+ *   best  [2][n_obj] float64: the maximum over those of mmdet's `bbox_overlaps(mode="iou",
+ *        eps=1e-6)` in float32 (`bbox_overlaps` restated from memory, unpinned; the device
+ *        function pn_triplet_match_boxes uses), as the exact float64 of that float32; 0 where
+ *        valid is 0.  Python's `max(row)`: the first value unless a later one is greater.
+ * Entry added at ABI 34. */
+int pn_eval_iou_best_boxes(const float* pred_boxes, int ld_pred, const int64_t* pred_labels, int R,
+                           const float* gt_boxes, int ld_gt, const int32_t* gt_labels, int n_obj,
+                           uint8_t* valid, double* best, void* stream);
+
+/* Evaluator feed, part 4 (csrc/nogc.hip): the no-graph-constraint ranking of
+ * `SGRecall.calculate_recall` (sgg_metrics.py:254-343), one launch per image.
+ *   det [2R] rows of ld >= 5 floats, the object score in column 4 (`refine_bboxes` as it is)
+ *   labels [2R] int64      rel_dists [R][C1] float32      sub_row / obj_row [R] int32 in [0, 2R)
+ *   per_row = the reference's `nogc_num`, 1 <= per_row <= C1 - 1      1 <= K <= 100 (:306-308)
+ * Candidate (r, c), c in 1..C1-1, scores (det[sub_row[r]][4] * det[obj_row[r]][4]) *
+ * rel_dists[r][c]: two separately rounded fp32 products in that order (:256-257).  It survives
+ * the per-row cut iff fewer than per_row candidates of its row beat it (:258-264).  The survivors
+ * are ranked in descending order and the first count = min(K, R * per_row) are written:
+ *   triplets [K][3] int32 = (labels[sub_row[r]], c, labels[obj_row[r]])
+ *   sub_rows / obj_rows [K] int32      scores [K] float32 (the product)      count [1] int32
+ * rows past count are filled with -1 (scores: 0).  Ties (numpy leaves them unspecified, so this
+ * is a documented choice, not parity): inside a row and in the ranking the candidate with the
+ * smaller (r, c) wins, -0 == +0 -- the rule of pn_topk_pairs.  Scores are finite.
+ * R * (C1 - 1) <= 65536.  No float atomics; the result is independent of execution order.
+ * Entry added at ABI 34. */
+int pn_nogc_triplets_f32(const float* det, int ld, const int64_t* labels, const float* rel_dists,
+                         const int32_t* sub_row, const int32_t* obj_row, int R, int C1,
+                         int per_row, int K, int32_t* triplets, int32_t* sub_rows,
+                         int32_t* obj_rows, float* scores, int32_t* count, void* stream);
 
 /* Panoptic quality (csrc/panoptic_quality.hip): one image's share of PQ / SQ / RQ, the metric of
  * the reference's `--eval PQ` (pairnet/datasets/psg.py:309-335 -> [3P] mmdet's panoptic

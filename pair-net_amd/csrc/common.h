@@ -127,3 +127,23 @@ __device__ __forceinline__ float tap_blend_fused(const Tap& ty, const Tap& tx, f
   const float top = fmaf(tx.l0, v00, tx.l1 * v01), bot = fmaf(tx.l0, v10, tx.l1 * v11);
   return fmaf(ty.l0, top, ty.l1 * bot);
 }
+
+// mmdet's `bbox_overlaps(mode="iou", eps=1e-6)` of one box pair in float32 (restated from memory,
+// unpinned): area = (x2 - x1) * (y2 - y1), overlap = clamp(rb - lt, 0) product, union clamped to
+// eps.  ONE definition for the box triplet match (postproc.hip) and the box IoU statistic
+// (nogc.hip), so that both round alike.
+__device__ __forceinline__ float box_iou_f32(float ax1, float ay1, float ax2, float ay2, float bx1,
+                                             float by1, float bx2, float by2) {
+  // no fma contraction: `union - w * h` must round the product first, like the reference's
+  // separate tensor ops.  Plain operators under the pragma: the *_rn intrinsics are inline
+  // header functions that carry the header's own (contractable) mode into the caller.
+#pragma clang fp contract(off)
+  const float a1 = (ax2 - ax1) * (ay2 - ay1);
+  const float a2 = (bx2 - bx1) * (by2 - by1);
+  const float w = fmaxf(fminf(ax2, bx2) - fmaxf(ax1, bx1), 0.f);
+  const float h = fmaxf(fminf(ay2, by2) - fmaxf(ay1, by1), 0.f);
+  const float ov = w * h;
+  const float sum = a1 + a2;
+  const float un = fmaxf(sum - ov, 1e-6f);
+  return ov / un;
+}

@@ -683,22 +683,7 @@ extern "C" int pn_triplet_match(const int32_t* pred_triplets, const int32_t* gt_
 // box-trunk sibling head's results): IoU as mmdet's `bbox_overlaps(mode="iou", eps=1e-6)` in
 // float32 -- area = (x2 - x1) * (y2 - y1), overlap = clamp(rb - lt, 0) product, union clamped
 // to eps -- and for phrase detection on the union boxes of subject and object (:1239-1259).
-__device__ __forceinline__ float box_iou_f32(float ax1, float ay1, float ax2, float ay2, float bx1,
-                                             float by1, float bx2, float by2) {
-  // no fma contraction: `union - w * h` must round the product first, like the reference's
-  // separate tensor ops.  Plain operators under the pragma: the *_rn intrinsics are inline
-  // header functions that carry the header's own (contractable) mode into the caller.
-#pragma clang fp contract(off)
-  const float a1 = (ax2 - ax1) * (ay2 - ay1);
-  const float a2 = (bx2 - bx1) * (by2 - by1);
-  const float w = fmaxf(fminf(ax2, bx2) - fmaxf(ax1, bx1), 0.f);
-  const float h = fmaxf(fminf(ay2, by2) - fmaxf(ay1, by1), 0.f);
-  const float ov = w * h;
-  const float sum = a1 + a2;
-  const float un = fmaxf(sum - ov, 1e-6f);
-  return ov / un;
-}
-
+// (box_iou_f32: common.h, shared with the box IoU statistic of csrc/nogc.hip)
 __global__ __launch_bounds__(256) void k_triplet_match_boxes(
     const int32_t* __restrict__ ptrip, const int32_t* __restrict__ gtrip, int P, int G,
     const float* __restrict__ pbox, int ldp, const float* __restrict__ gbox, int ldg,

@@ -17,6 +17,11 @@ subject / object IoU statistic (`_compute_iou_panseg`, :1087-1131, from the same
 popcounts).  Images without ground-truth relations are skipped, as the reference's
 `sgg_evaluate` loop does.
 
+Box results (`detection_method="bbox"`) get what the reference adds for them: the
+no-graph-constraint recalls (:254-343; `nogc=`, ranked on the device by csrc/nogc.hip) and the
+box IoU statistic (`_compute_iou_bbox`, :1133-1178; `iou=`), on `evaluate_boxes`,
+`SceneGraphMetrics` and `StreamingEvaluator.add_boxes`; both are off by default.
+
 `PanopticQuality` is the reference's other metric, `--eval PQ` (pairnet/datasets/psg.py:309-335):
 PQ / SQ / RQ of the panoptic maps, from a per-image record csrc/panoptic_quality.hip leaves on
 the device.
@@ -31,6 +36,33 @@ def _tensor(x):
     """Ground truth as handed in: numpy, lists, or tensors (host or ALREADY on the device, as
     `pairnet_amd.dataset.eval_ground_truth` leaves the masks)."""
     return x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+
+
+NOGC_TOP = 100      # the reference counts only the best 100 no-graph-constraint triplets
+#                     (`pred_to_gt[:100]`, sgg_metrics.py:306-308, :314, :333, :339)
+
+
+def nogc_thresholds(nogc, num_predicates, ks):
+    """The `nogc` keyword as a tuple of thresholds (the reference's `nogc_thres_num`): None ->
+    (), True -> the reference's default `(num_predicates,)` (sgg_eval.py:74-75), an int or up to
+    4 distinct ints in [1, num_predicates].  The reference truncates the ranked list at 100
+    whatever k is; here a k above 100 is refused instead of being truncated quietly."""
+    if nogc is None or nogc is False:
+        return ()
+    if nogc is True:
+        ts = (int(num_predicates),)
+    elif isinstance(nogc, (int, np.integer)):
+        ts = (int(nogc),)
+    else:
+        ts = tuple(int(t) for t in nogc)
+    if not 1 <= len(ts) <= 4 or len(set(ts)) != len(ts):
+        raise ValueError("nogc: 1..4 distinct thresholds, got %r" % (ts,))
+    if min(ts) < 1 or max(ts) > int(num_predicates):
+        raise ValueError("nogc: thresholds must lie in [1, %d], got %r" % (num_predicates, ts))
+    if any(int(k) > NOGC_TOP for k in ks):
+        raise ValueError("nogc: only the best %d triplets are ranked (sgg_metrics.py:306-308); "
+                         "k = %r is not served" % (NOGC_TOP, tuple(ks)))
+    return ts
 
 
 class TripletEvaluator:
@@ -94,35 +126,111 @@ class TripletEvaluator:
         det, labels, r_dists = result[0], result[1], result[5]
         dev = det.device
         R, C1 = r_dists.shape
-        gt_rels = _tensor(gt_rels).cpu().to(torch.int64)
-        gt_labels = _tensor(gt_labels).cpu().to(torch.int64)
-        G = int(gt_rels.shape[0])
-        gbox = torch.as_tensor(np.asarray(gt_boxes), dtype=torch.float32).to(dev).contiguous()
-        i32 = lambda t: t.to(torch.int32).to(dev).contiguous()
-        gtrip = i32(torch.stack([gt_labels[gt_rels[:, 0]], gt_rels[:, 2],
-                                 gt_labels[gt_rels[:, 1]]], 1))
+        G, gtrip, gs, go, gbox = self._box_ground_truth(gt_rels, gt_labels, gt_boxes, dev)
         ptrip = torch.empty(R, 3, device=dev, dtype=torch.int32)
         score = torch.empty(R, device=dev, dtype=torch.float32)
         hip.pred_triplets(labels, r_dists, ptrip, score, R, C1)
         ar = torch.arange(R, dtype=torch.int32, device=dev)
         match = torch.empty(R, G, device=dev, dtype=torch.uint8)
         hip.triplet_match_boxes(ptrip, gtrip, R, G, det, det.stride(0), gbox, 4, ar, ar + R,
-                                i32(gt_rels[:, 0]), i32(gt_rels[:, 1]), self.iou_thr, phrdet,
-                                ignore_rel, match)
+                                gs, go, self.iou_thr, phrdet, ignore_rel, match)
         return match
 
-    def evaluate_boxes(self, result, gt_rels, gt_labels, gt_boxes):
-        """sgdet + phrdet recalls of one image from box results (the graph-constrained part of
-        `calculate_recall`, sgg_metrics.py:173-252)."""
+    @staticmethod
+    def _box_ground_truth(gt_rels, gt_labels, gt_boxes, dev):
+        """(G, gt triplets [G][3], subject rows [G], object rows [G] int32, boxes [n_obj][4]
+        float32) on the device."""
+        gt_rels = _tensor(gt_rels).cpu().to(torch.int64)
+        gt_labels = _tensor(gt_labels).cpu().to(torch.int64)
+        gbox = torch.as_tensor(np.asarray(gt_boxes), dtype=torch.float32).to(dev).contiguous()
+        i32 = lambda t: t.to(torch.int32).to(dev).contiguous()
+        gtrip = i32(torch.stack([gt_labels[gt_rels[:, 0]], gt_rels[:, 2],
+                                 gt_labels[gt_rels[:, 1]]], 1))
+        return int(gt_rels.shape[0]), gtrip, i32(gt_rels[:, 0]), i32(gt_rels[:, 1]), gbox
+
+    @torch.no_grad()
+    @hip.on_device
+    def match_boxes_nogc(self, result, gt_rels, gt_labels, gt_boxes, per_row):
+        """The no-graph-constraint part of `calculate_recall` (sgg_metrics.py:254-343) for one
+        threshold `per_row` (the reference's `nogc_num`): the best `NOGC_TOP` of the R x
+        `per_row` surviving (pair, predicate) candidates, ranked on the device
+        (`pn_nogc_triplets_f32`) and matched as sgdet and as phrdet.  Returns the two uint8 match
+        matrices [P][G], P = min(NOGC_TOP, R * per_row)."""
+        det, labels, r_dists = result[0], result[1], result[5]
+        dev = det.device
+        R, C1 = r_dists.shape
+        G, gtrip, gs, go, gbox = self._box_ground_truth(gt_rels, gt_labels, gt_boxes, dev)
+        K = NOGC_TOP
+        P = min(K, R * int(per_row))
+        e32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int32)
+        trip, srow, orow, count = e32(K, 3), e32(K), e32(K), e32(1)
+        score = torch.empty(K, device=dev, dtype=torch.float32)
+        ar = torch.arange(R, dtype=torch.int32, device=dev)      # rel_pairs[r] = (r, R + r)
+        hip.nogc_triplets(det, det.stride(0), labels, r_dists.contiguous(), ar, ar + R, R, C1,
+                          int(per_row), K, trip, srow, orow, score, count)
+        out = []
+        for ph in (False, True):
+            match = torch.empty(P, G, device=dev, dtype=torch.uint8)
+            hip.triplet_match_boxes(trip, gtrip, P, G, det, det.stride(0), gbox, 4, srow, orow,
+                                    gs, go, self.iou_thr, ph, False, match)
+            out.append(match)
+        return out[0], out[1]
+
+    @torch.no_grad()
+    @hip.on_device
+    def iou_stats_boxes(self, result, gt_labels, gt_boxes):
+        """`SGObjectIOU.calculate_iou` -> `_compute_iou_bbox` (sgg_metrics.py:1025-1028,
+        :1133-1178): for every ground-truth OBJECT whose class occurs among the subject (object)
+        predictions, the best box IoU over the predictions of that class.  Returns two float64
+        arrays (subjects, objects), in ground-truth object order, each the exact value of the
+        reference's float32."""
+        det, labels = result[0], result[1]
+        dev = det.device
+        R = int(labels.shape[0]) // 2
+        lab = torch.as_tensor(np.asarray(gt_labels)).reshape(-1).to(torch.int32).to(dev)
+        nobj = int(lab.shape[0])
+        if nobj == 0:
+            return np.zeros(0), np.zeros(0)
+        gbox = torch.as_tensor(np.asarray(gt_boxes), dtype=torch.float32).reshape(nobj, 4)
+        gbox = gbox.to(dev).contiguous()
+        valid = torch.empty(2 * nobj, device=dev, dtype=torch.uint8)
+        best = torch.empty(2 * nobj, device=dev, dtype=torch.float64)
+        hip.eval_iou_best_boxes(det, det.stride(0), labels, R, gbox, 4, lab, nobj, valid, best)
+        valid, best = valid.cpu().numpy().astype(bool), best.cpu().numpy()
+        return best[:nobj][valid[:nobj]], best[nobj:][valid[nobj:]]
+
+    def evaluate_boxes(self, result, gt_rels, gt_labels, gt_boxes, nogc=None, iou=False):
+        """sgdet + phrdet recalls of one image from box results (`calculate_recall`,
+        sgg_metrics.py:173-252).  `nogc` (see `nogc_thresholds`) adds the no-graph-constraint
+        part (:254-343), per threshold t the reference's `local_container` keys
+        "nogc@t_pred_to_gt" / "phrdet_nogc@t_pred_to_gt" (lists of at most 100 lists) and
+        "nogc@t_recall" / "phrdet_nogc@t_recall"; `iou=True` adds "sub_iou" / "obj_iou"
+        (`iou_stats_boxes`).  The reference's "..._all_pred_to_gt" and "..._pred_pair_in_gt"
+        entries feed only `SGPairAccuracy`, which does nothing in sgdet mode: left out."""
         n = len(gt_rels)
+        R, C1 = (int(v) for v in result[5].shape)
+        ts = nogc_thresholds(nogc, C1 - 1, self.ks)
         if n == 0:
-            R = int(result[5].shape[0])
-            return dict(pred_to_gt=[[] for _ in range(R)], phrdet_pred_to_gt=[[] for _ in range(R)],
-                        sgdet_recall=None, phrdet_recall=None)
+            out = dict(pred_to_gt=[[] for _ in range(R)], phrdet_pred_to_gt=[[] for _ in range(R)],
+                       sgdet_recall=None, phrdet_recall=None)
+            for t in ts:
+                for pre in ("", "phrdet_"):
+                    out[pre + "nogc@%d_pred_to_gt" % t] = [[] for _ in range(min(NOGC_TOP, R * t))]
+                    out[pre + "nogc@%d_recall" % t] = None
+            return out
         p2g = self.pred_to_gt(self.match_boxes(result, gt_rels, gt_labels, gt_boxes))
         ph = self.pred_to_gt(self.match_boxes(result, gt_rels, gt_labels, gt_boxes, phrdet=True))
-        return dict(pred_to_gt=p2g, phrdet_pred_to_gt=ph, sgdet_recall=self.recall(p2g, n),
-                    phrdet_recall=self.recall(ph, n))
+        out = dict(pred_to_gt=p2g, phrdet_pred_to_gt=ph, sgdet_recall=self.recall(p2g, n),
+                   phrdet_recall=self.recall(ph, n))
+        for t in ts:
+            ms = self.match_boxes_nogc(result, gt_rels, gt_labels, gt_boxes, t)
+            for pre, m in zip(("", "phrdet_"), ms):
+                lists = self.pred_to_gt(m)
+                out[pre + "nogc@%d_pred_to_gt" % t] = lists
+                out[pre + "nogc@%d_recall" % t] = self.recall(lists, n)
+        if iou:
+            out["sub_iou"], out["obj_iou"] = self.iou_stats_boxes(result, gt_labels, gt_boxes)
+        return out
 
     def pred_to_gt(self, match):
         """The reference's list of lists (one D2H copy of R x G bytes)."""
@@ -209,17 +317,26 @@ class SceneGraphMetrics:
                                  "phrdet_recall": ..., "phrdet_mean_recall": ..., "images": n}
     """
 
-    def __init__(self, num_predicates, ks=(20, 50, 100)):
+    def __init__(self, num_predicates, ks=(20, 50, 100), nogc=None):
         self.num_rel = int(num_predicates) + 1        # + __background__ (:681-683)
         self.ks = tuple(ks)
         self.recalls = {m: {k: [] for k in self.ks} for m in ("sgdet", "phrdet")}
         self.collect = {m: {k: [[] for _ in range(self.num_rel)] for k in self.ks}
                         for m in ("sgdet", "phrdet")}
+        # the reference's `nogc_result_dict` (:69-79, :698-735): the same two containers once
+        # per no-graph-constraint threshold (box results only)
+        self.nogc = nogc_thresholds(nogc, int(num_predicates), self.ks)
+        self.nogc_recalls = {t: {m: {k: [] for k in self.ks} for m in ("sgdet", "phrdet")}
+                             for t in self.nogc}
+        self.nogc_collect = {t: {m: {k: [[] for _ in range(self.num_rel)] for k in self.ks}
+                                 for m in ("sgdet", "phrdet")} for t in self.nogc}
         self.sub_iou, self.obj_iou = [], []
         self.images = self.skipped = 0
 
-    def _collect(self, mode, pred_to_gt, gt_rels):
-        """`SGMeanRecall._collect_single` (:741-766)."""
+    def _collect(self, mode, pred_to_gt, gt_rels, target=None):
+        """`SGMeanRecall._collect_single` (:741-766); `target`: the container of one
+        no-graph-constraint threshold instead of the graph-constrained one."""
+        collect = self.collect if target is None else target
         for k in self.ks:
             match = set()
             for lst in pred_to_gt[:k]:
@@ -233,11 +350,13 @@ class SceneGraphMetrics:
                 hit[0] += 1
             for n in range(self.num_rel):
                 if count[n] > 0:
-                    self.collect[mode][k][n].append(float(hit[n] / count[n]))
+                    collect[mode][k][n].append(float(hit[n] / count[n]))
 
     def add(self, image_eval, gt_rels, iou=None):
         """`image_eval`: what `TripletEvaluator.__call__` / `evaluate_boxes` returned for the
-        image; `iou`: optionally `TripletEvaluator.iou_stats(...)` of the same image."""
+        image (with `nogc` set: `evaluate_boxes(..., nogc=...)` with at least these thresholds);
+        `iou`: optionally `TripletEvaluator.iou_stats(...)` of the same image (default: the
+        "sub_iou" / "obj_iou" entries `evaluate_boxes(..., iou=True)` left, if any)."""
         gt_rels = np.asarray(gt_rels).reshape(-1, 3)
         if gt_rels.shape[0] == 0:
             self.skipped += 1
@@ -247,6 +366,14 @@ class SceneGraphMetrics:
             for k in self.ks:
                 self.recalls[mode][k].append(image_eval[mode + "_recall"][k])
             self._collect(mode, image_eval[key], gt_rels)
+        for t in self.nogc:                       # (:312-319, :337-343, :882-899)
+            for mode, pre in (("sgdet", ""), ("phrdet", "phrdet_")):
+                for k in self.ks:
+                    self.nogc_recalls[t][mode][k].append(image_eval[pre + "nogc@%d_recall" % t][k])
+                self._collect(mode, image_eval[pre + "nogc@%d_pred_to_gt" % t], gt_rels,
+                              target=self.nogc_collect[t])
+        if iou is None and "sub_iou" in image_eval:
+            iou = (image_eval["sub_iou"], image_eval["obj_iou"])
         if iou is not None:
             self.sub_iou.extend(iou[0])
             self.obj_iou.extend(iou[1])
@@ -254,17 +381,26 @@ class SceneGraphMetrics:
     def summary(self):
         """`SGRecall._print_single` / `SGMeanRecall._calculate_single` (:768-792)."""
         out = dict(images=self.images, skipped=self.skipped)
-        for mode in ("sgdet", "phrdet"):
-            out[mode + "_recall"] = {k: float(np.mean(v)) if v else 0.0
-                                     for k, v in self.recalls[mode].items()}
-            mr, lists = {}, {}
-            for k in self.ks:
-                per = self.collect[mode][k]
-                lst = [0.0 if len(per[n + 1]) == 0 else float(np.mean(per[n + 1]))
-                       for n in range(self.num_rel - 1)]
-                lists[k] = lst
-                mr[k] = sum(lst) / float(self.num_rel - 1)
-            out[mode + "_mean_recall"], out[mode + "_mean_recall_list"] = mr, lists
+
+        def fill(dst, recalls, collect):
+            for mode in ("sgdet", "phrdet"):
+                dst[mode + "_recall"] = {k: float(np.mean(v)) if v else 0.0
+                                         for k, v in recalls[mode].items()}
+                mr, lists = {}, {}
+                for k in self.ks:
+                    per = collect[mode][k]
+                    lst = [0.0 if len(per[n + 1]) == 0 else float(np.mean(per[n + 1]))
+                           for n in range(self.num_rel - 1)]
+                    lists[k] = lst
+                    mr[k] = sum(lst) / float(self.num_rel - 1)
+                dst[mode + "_mean_recall"], dst[mode + "_mean_recall_list"] = mr, lists
+
+        fill(out, self.recalls, self.collect)
+        if self.nogc:                             # the reference's `nogc_result_dict`
+            out["nogc"] = {}
+            for t in self.nogc:
+                out["nogc"][t] = {}
+                fill(out["nogc"][t], self.nogc_recalls[t], self.nogc_collect[t])
         if self.sub_iou or self.obj_iou:
             out["subject-IoU"] = float(np.mean(self.sub_iou)) if self.sub_iou else 0.0
             out["object-IoU"] = float(np.mean(self.obj_iou)) if self.obj_iou else 0.0
@@ -280,25 +416,35 @@ class SceneGraphMetrics:
         return (p[:, None] == g[None, :]).sum(-1) > 0
 
 
-def host_record(image_eval, gt_rels, num_rel, ks=(20, 50, 100)):
+def host_record(image_eval, gt_rels, num_rel, ks=(20, 50, 100), nogc=None):
     """One image's recall record in numpy, from the `pred_to_gt` lists `TripletEvaluator`
     returned: (hits [2][len(ks)][num_rel], counts [num_rel]) int32 -- what `pn_eval_record`
     leaves on the device (`reduce(np.union1d, pred_to_gt[:k])`, sgg_metrics.py:95-99, fed
-    through `_collect_single`, :741-766; slot 0 counts every predicate)."""
+    through `_collect_single`, :741-766; slot 0 counts every predicate).  With `nogc` (a tuple
+    of thresholds) a third array follows: nogc_hits [len(nogc)][2][len(ks)][num_rel], the same
+    counts from the "nogc@t_pred_to_gt" / "phrdet_nogc@t_pred_to_gt" lists."""
     gt_rels = np.asarray(gt_rels).reshape(-1, 3)
     pred = gt_rels[:, 2].astype(np.int64)
-    hits = np.zeros((2, len(ks), num_rel), np.int32)
     counts = np.zeros(num_rel, np.int32)
     np.add.at(counts, pred, 1)
     counts[0] = gt_rels.shape[0]
-    for m, key in enumerate(("pred_to_gt", "phrdet_pred_to_gt")):
-        for j, k in enumerate(ks):
-            lists = image_eval[key][:k]
-            match = np.unique(np.concatenate([np.asarray(l, np.int64) for l in lists]
-                                             + [np.zeros(0, np.int64)]))
-            np.add.at(hits[m, j], pred[match], 1)
-            hits[m, j, 0] = match.shape[0]
-    return hits, counts
+
+    def hits_of(keys):
+        hits = np.zeros((2, len(ks), num_rel), np.int32)
+        for m, key in enumerate(keys):
+            for j, k in enumerate(ks):
+                lists = image_eval[key][:k]
+                match = np.unique(np.concatenate([np.asarray(l, np.int64) for l in lists]
+                                                 + [np.zeros(0, np.int64)]))
+                np.add.at(hits[m, j], pred[match], 1)
+                hits[m, j, 0] = match.shape[0]
+        return hits
+
+    hits = hits_of(("pred_to_gt", "phrdet_pred_to_gt"))
+    if not nogc:
+        return hits, counts
+    more = [hits_of(("nogc@%d_pred_to_gt" % t, "phrdet_nogc@%d_pred_to_gt" % t)) for t in nogc]
+    return hits, counts, np.stack(more)
 
 
 class StreamingEvaluator:
@@ -316,22 +462,41 @@ class StreamingEvaluator:
         ev.summary()
 
     Several ranks: `ev.merge(all ranks' ev.state())` on rank 0, then `ev.summary()`.
-    Per-image `pred_to_gt` lists are not produced; `TripletEvaluator` stays for those."""
+    Per-image `pred_to_gt` lists are not produced; `TripletEvaluator` stays for those.
+
+    Box results: `ev.add_boxes(result, gt_rels, gt_labels, gt_boxes, index=i, iou=True)`; an
+    evaluator built with `nogc=` also records the no-graph-constraint ranking per threshold
+    (`summary()["nogc"]`), and then takes box results only."""
 
     _MAGIC = 0x5345                              # first word of a state blob
+    _MAGIC_NOGC = 0x534E                         # ... of one that carries nogc thresholds
 
-    def __init__(self, num_predicates, ks=(20, 50, 100), iou_thr=0.5):
+    def __init__(self, num_predicates, ks=(20, 50, 100), iou_thr=0.5, nogc=None):
+        """`nogc` (see `nogc_thresholds`; box results only): `add_boxes` also leaves, per
+        threshold, the record of the no-graph-constraint ranking (sgg_metrics.py:254-343), and
+        `summary()` gains the `"nogc"` entry of `SceneGraphMetrics`."""
         self.num_predicates = int(num_predicates)
         self.num_rel = self.num_predicates + 1   # + __background__ (:681-683)
         self.ks = tuple(int(k) for k in ks)
         self.iou_thr = float(iou_thr)
         if not 1 <= len(self.ks) <= 8 or not 2 <= self.num_rel <= 256:
             raise ValueError("StreamingEvaluator: 1..8 values of k and at most 255 predicates")
-        self._host = {}       # index -> (G, ints [2 nk num_rel + num_rel] int32, sub f64, obj f64)
+        self.nogc = nogc_thresholds(nogc, self.num_predicates, self.ks)
+        # ints per image: [hits 2 nk num_rel | counts num_rel | per threshold: hits 2 nk num_rel]
+        self._nhits = 2 * len(self.ks) * self.num_rel
+        self._nints = self._nhits + self.num_rel + len(self.nogc) * self._nhits
+        self._host = {}       # index -> (G, ints [_nints] int32, sub f64, obj f64)
         self._skipped = set()
-        self._dev = []        # (index, G, record, valid, best, event): not read back yet
+        self._dev = []        # (index, G, record, valid, best, event, IoU rows): not read back yet
         self._seen = set()    # every index added so far
         self._calls = 0
+
+    def _config(self):
+        """(magic, the header words behind [magic, images, skipped]): without `nogc` today's
+        (nk, num_rel); with it another magic and the thresholds appended."""
+        if not self.nogc:
+            return self._MAGIC, [len(self.ks), self.num_rel]
+        return self._MAGIC_NOGC, [len(self.ks), self.num_rel, len(self.nogc)] + list(self.nogc)
 
     # ---- ground truth: checked on the host, one pinned buffer, one non-blocking copy ----
     def _tables(self, gt_rels, gt_labels):
@@ -373,16 +538,18 @@ class StreamingEvaluator:
         self._seen.add(idx)
         return idx
 
-    def _log(self, idx, G, rec, valid, best):
+    def _log(self, idx, G, rec, valid, best, iou_rows=None):
+        """`iou_rows`: rows per side of valid / best (G on the mask path: one per relation;
+        n_obj on the box path: one per object)."""
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(rec.device))
-        self._dev.append((idx, G, rec, valid, best, ev))
+        self._dev.append((idx, G, rec, valid, best, ev, G if iou_rows is None else iou_rows))
 
     def _record(self, m_s, m_p, R, G, gpred, ks, dev):
         nk = len(self.ks)
-        rec = torch.empty((2 * nk + 1) * self.num_rel, device=dev, dtype=torch.int32)
+        rec = torch.empty(self._nints, device=dev, dtype=torch.int32)
         hip.eval_record(m_s, m_p, R, G, gpred, ks, nk, self.num_rel,
-                        rec[:2 * nk * self.num_rel], rec[2 * nk * self.num_rel:])
+                        rec[:self._nhits], rec[self._nhits:self._nhits + self.num_rel])
         return rec
 
     @torch.no_grad()
@@ -392,6 +559,11 @@ class StreamingEvaluator:
         (n_obj,) host data; gt_masks (n_obj, H, W) bool, on the device as
         `dataset.eval_ground_truth` leaves them (host masks go up non-blocking).  Everything is
         enqueued on the current stream; nothing is read back."""
+        if self.nogc:
+            raise NotImplementedError(
+                "StreamingEvaluator.add: no-graph-constraint recalls exist for box results only "
+                "(the reference computes none for detection_method == \"pan_seg\", "
+                "sgg_metrics.py:254); use add_boxes, or an evaluator without nogc")
         labels, masks, r_dists = result[1], result[3], result[7]
         dev = masks.device
         R, C1 = r_dists.shape
@@ -443,12 +615,18 @@ class StreamingEvaluator:
 
     @torch.no_grad()
     @hip.on_device
-    def add_boxes(self, result, gt_rels, gt_labels, gt_boxes, index=None):
+    def add_boxes(self, result, gt_rels, gt_labels, gt_boxes, index=None, iou=False):
         """`detection_method="bbox"`: result = the 6-tuple of `CrossHeadBBox.get_bboxes`;
-        gt_boxes (n_obj, 4) xyxy host data.  No IoU statistic (the host path has none)."""
+        gt_boxes (n_obj, 4) xyxy host data.  With `nogc` set, per threshold one ranking
+        (`pn_nogc_triplets_f32`), two matches and one `pn_eval_record` more; `iou=True` also
+        enqueues the box IoU statistic (`pn_eval_iou_best_boxes`: one row per ground-truth
+        OBJECT).  Everything goes to the current stream; nothing is read back."""
         det, labels, r_dists = result[0], result[1], result[5]
         dev = det.device
         R, C1 = r_dists.shape
+        if self.nogc and C1 - 1 != self.num_predicates:
+            raise ValueError("add_boxes: rel_dists has %d predicates, the evaluator %d"
+                             % (C1 - 1, self.num_predicates))
         rels, lab, G, nobj = self._tables(gt_rels, gt_labels)
         idx = self._index(index)
         if G == 0:
@@ -465,7 +643,34 @@ class StreamingEvaluator:
         for ph in (0, 1):
             hip.triplet_match_boxes(ptrip, gtrip, R, G, det, det.stride(0), gbox, 4, ar[:R],
                                     ar[R:2 * R], gs, go, self.iou_thr, bool(ph), False, m[ph])
-        self._log(idx, G, self._record(m[0], m[1], R, G, gpred, ks, dev), None, None)
+        rec = self._record(m[0], m[1], R, G, gpred, ks, dev)
+        if self.nogc:
+            K, nk = NOGC_TOP, len(self.ks)
+            i32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int32)
+            trip, srow, orow, count = i32(len(self.nogc), K, 3), i32(len(self.nogc), K), \
+                i32(len(self.nogc), K), i32(len(self.nogc))
+            nscore = torch.empty(len(self.nogc), K, device=dev, dtype=torch.float32)
+            spare = i32(self.num_rel)             # (pn_eval_record writes the counts again)
+            rd = r_dists.contiguous()
+            for j, t in enumerate(self.nogc):
+                P = min(K, R * t)                 # = count[j], known without reading it
+                hip.nogc_triplets(det, det.stride(0), labels, rd, ar[:R], ar[R:2 * R], R, C1, t,
+                                  K, trip[j], srow[j], orow[j], nscore[j], count[j:j + 1])
+                mt = torch.empty(2, P, G, device=dev, dtype=torch.uint8)
+                for ph in (0, 1):
+                    hip.triplet_match_boxes(trip[j], gtrip, P, G, det, det.stride(0), gbox, 4,
+                                            srow[j], orow[j], gs, go, self.iou_thr, bool(ph),
+                                            False, mt[ph])
+                o = self._nhits + self.num_rel + j * self._nhits
+                hip.eval_record(mt[0], mt[1], P, G, gpred, ks, nk, self.num_rel,
+                                rec[o:o + self._nhits], spare)
+        valid = best = None
+        if iou:
+            valid = torch.empty(2 * nobj, device=dev, dtype=torch.uint8)
+            best = torch.empty(2 * nobj, device=dev, dtype=torch.float64)
+            hip.eval_iou_best_boxes(det, det.stride(0), labels, R, gbox, 4, glab, nobj, valid,
+                                    best)
+        self._log(idx, G, rec, valid, best, iou_rows=nobj)
 
     def add_host(self, index, image_eval, gt_rels, iou=None):
         """The same record computed in numpy from what `TripletEvaluator.__call__` /
@@ -478,9 +683,11 @@ class StreamingEvaluator:
             return
         if rels[:, 2].min() < 1 or rels[:, 2].max() >= self.num_rel:
             raise ValueError("gt_rels: predicate ids must lie in [1, %d)" % self.num_rel)
-        hits, counts = host_record(image_eval, rels, self.num_rel, self.ks)
+        parts = host_record(image_eval, rels, self.num_rel, self.ks, nogc=self.nogc)
+        if iou is None and "sub_iou" in image_eval:
+            iou = (image_eval["sub_iou"], image_eval["obj_iou"])
         sub, obj = (np.zeros(0), np.zeros(0)) if iou is None else iou
-        self._host[idx] = (int(rels.shape[0]), np.concatenate([hits.reshape(-1), counts]),
+        self._host[idx] = (int(rels.shape[0]), np.concatenate([p.reshape(-1) for p in parts]),
                            np.asarray(sub, np.float64).reshape(-1),
                            np.asarray(obj, np.float64).reshape(-1))
 
@@ -491,7 +698,7 @@ class StreamingEvaluator:
         dev = self._dev[0][2].device
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
-            for _, _, rec, valid, best, ev in self._dev:
+            for _, _, rec, valid, best, ev, _ in self._dev:
                 # add() may have run on other streams (the pipeline's chain streams): order
                 # this stream behind each of them, and tell the allocator who reads the blocks
                 cur.wait_event(ev)
@@ -504,32 +711,41 @@ class StreamingEvaluator:
                 valid = torch.cat([d[3] for d in with_iou]).cpu().numpy().astype(bool)
                 best = torch.cat([d[4] for d in with_iou]).cpu().numpy()
         o = 0
-        for i, (idx, G, _, v, _, _) in enumerate(self._dev):
+        for i, (idx, G, _, v, _, _, rows) in enumerate(self._dev):
             sub = obj = np.zeros(0)
-            if v is not None:
-                sub = best[o:o + G][valid[o:o + G]]
-                obj = best[o + G:o + 2 * G][valid[o + G:o + 2 * G]]
-                o += 2 * G
+            if v is not None:                 # rows per side: G (masks) or n_obj (boxes)
+                sub = best[o:o + rows][valid[o:o + rows]]
+                obj = best[o + rows:o + 2 * rows][valid[o + rows:o + 2 * rows]]
+                o += 2 * rows
             self._host[idx] = (G, recs[i], sub, obj)
         self._dev = []
 
     def records(self):
         """{index: dict(G, hits [2][nk][num_rel], counts [num_rel], sub_iou, obj_iou)} of the
-        images added so far (waits for the GPU)."""
+        images added so far (waits for the GPU); with `nogc` also nogc_hits
+        {threshold: [2][nk][num_rel]}."""
         self._flush()
-        n = 2 * len(self.ks) * self.num_rel
-        return {idx: dict(G=G, hits=ints[:n].reshape(2, len(self.ks), self.num_rel),
-                          counts=ints[n:], sub_iou=sub, obj_iou=obj)
-                for idx, (G, ints, sub, obj) in self._host.items()}
+        n, nr, shape = self._nhits, self.num_rel, (2, len(self.ks), self.num_rel)
+        out = {}
+        for idx, (G, ints, sub, obj) in self._host.items():
+            out[idx] = dict(G=G, hits=ints[:n].reshape(shape), counts=ints[n:n + nr],
+                            sub_iou=sub, obj_iou=obj)
+            if self.nogc:
+                out[idx]["nogc_hits"] = {
+                    t: ints[n + nr + j * n:n + nr + (j + 1) * n].reshape(shape)
+                    for j, t in enumerate(self.nogc)}
+        return out
 
     def state(self):
         """Everything added so far as ONE float64 array (int32 values are exact in it):
         [magic, images, skipped, nk, num_rel | per image: index, G, n_sub, n_obj, record,
         sub IoUs, obj IoUs | skipped indices].  The only place the class waits for the GPU;
-        three device-to-host copies however many images there are."""
+        three device-to-host copies however many images there are.  With `nogc` the magic word
+        is another one, the header goes on with [number of thresholds, thresholds...], and the
+        record is the longer one (`host_record(..., nogc=...)`)."""
         self._flush()
-        parts = [np.array([self._MAGIC, len(self._host), len(self._skipped), len(self.ks),
-                           self.num_rel], np.float64)]
+        magic, config = self._config()
+        parts = [np.array([magic, len(self._host), len(self._skipped)] + config, np.float64)]
         for idx in sorted(self._host):
             G, ints, sub, obj = self._host[idx]
             parts += [np.array([idx, G, sub.shape[0], obj.shape[0]], np.float64),
@@ -542,13 +758,15 @@ class StreamingEvaluator:
         all ranks, its own among them).  An image present in two blobs is an error."""
         self._flush()
         host, skipped = {}, set()
-        n = (2 * len(self.ks) + 1) * self.num_rel
+        n = self._nints
+        magic, config = self._config()
+        head = 3 + len(config)
         for blob in states:
             blob = np.asarray(blob, np.float64)
-            if blob.shape[0] < 5 or int(blob[0]) != self._MAGIC or \
-                    (int(blob[3]), int(blob[4])) != (len(self.ks), self.num_rel):
+            if blob.shape[0] < head or int(blob[0]) != magic or \
+                    [int(v) for v in blob[3:head]] != config:
                 raise ValueError("StreamingEvaluator.merge: not a state of this configuration")
-            o = 5
+            o = head
             for _ in range(int(blob[1])):
                 idx, G, ns, no = (int(v) for v in blob[o:o + 4])
                 o += 4
@@ -569,19 +787,26 @@ class StreamingEvaluator:
         in dataset order: its lists are rebuilt from the records with the reference's float
         expressions (`hits / float(G)`, `float(hit / count)`), its own code does the rest."""
         self._flush()
-        m = SceneGraphMetrics(self.num_predicates, self.ks)
-        nk, nr = len(self.ks), self.num_rel
-        for idx in sorted(self._host):
-            G, ints, sub, obj = self._host[idx]
-            hits, counts = ints[:2 * nk * nr].reshape(2, nk, nr), ints[2 * nk * nr:]
-            m.images += 1
+        m = SceneGraphMetrics(self.num_predicates, self.ks, nogc=self.nogc or None)
+        nk, nr, nh = len(self.ks), self.num_rel, self._nhits
+
+        def rebuild(hits, counts, G, recalls, collect):
             for mi, mode in enumerate(("sgdet", "phrdet")):
                 for j, k in enumerate(self.ks):
-                    m.recalls[mode][k].append(int(hits[mi, j, 0]) / float(G))
+                    recalls[mode][k].append(int(hits[mi, j, 0]) / float(G))
                     for n in range(nr):
                         if counts[n] > 0:
-                            m.collect[mode][k][n].append(
-                                float(int(hits[mi, j, n]) / int(counts[n])))
+                            collect[mode][k][n].append(float(int(hits[mi, j, n]) / int(counts[n])))
+
+        for idx in sorted(self._host):
+            G, ints, sub, obj = self._host[idx]
+            counts = ints[nh:nh + nr]
+            m.images += 1
+            rebuild(ints[:nh].reshape(2, nk, nr), counts, G, m.recalls, m.collect)
+            for j, t in enumerate(self.nogc):
+                o = nh + nr + j * nh
+                rebuild(ints[o:o + nh].reshape(2, nk, nr), counts, G, m.nogc_recalls[t],
+                        m.nogc_collect[t])
             m.sub_iou.extend(sub)
             m.obj_iou.extend(obj)
         m.skipped = len(self._skipped)

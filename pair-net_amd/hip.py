@@ -205,6 +205,9 @@ _SIGS = {
     "pn_eval_record": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "pn_eval_iou_best": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
                                    _vp]),
+    "pn_eval_iou_best_boxes": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "pn_nogc_triplets_f32": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
+                                       _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn_pan_masks_u8": (C.c_int, [_vp] * 5 + [_i32] * 3 + [_vp]),
     "pn_preprocess_u8_f32": (C.c_int, [_vp, _i32, _i32, _vp] + [_i32] * 4 + [C.POINTER(_f32),
                                                                             C.POINTER(_f32), _i32, _vp]),
@@ -1263,6 +1266,37 @@ def eval_iou_best(inter, area_p, area_g, P, n_obj, pred_labels, gt_labels, gs, g
                                   _ptr(pred_labels, torch.int64), _ptr(gt_labels, i32),
                                   _ptr(gs, i32), _ptr(go, i32), G, _ptr(valid, torch.uint8),
                                   _ptr(best, torch.float64), _stream()), "pn_eval_iou_best")
+
+
+def eval_iou_best_boxes(pbox, ldp, pred_labels, R, gbox, ldg, gt_labels, n_obj, valid, best):
+    """valid [2][n_obj] uint8, best [2][n_obj] float64: per side and ground-truth OBJECT the best
+    box IoU over the predictions of its class (side 0: rows [0, R) of pbox, side 1: [R, 2R))."""
+    assert pred_labels.numel() >= 2 * R and gt_labels.numel() >= n_obj
+    assert pbox.numel() >= (2 * R - 1) * ldp + 4 and gbox.numel() >= (n_obj - 1) * ldg + 4
+    assert valid.numel() == 2 * n_obj and best.numel() == 2 * n_obj
+    _check(lib().pn_eval_iou_best_boxes(_ptr(pbox), ldp, _ptr(pred_labels, torch.int64), R,
+                                        _ptr(gbox), ldg, _ptr(gt_labels, torch.int32), n_obj,
+                                        _ptr(valid, torch.uint8), _ptr(best, torch.float64),
+                                        _stream()), "pn_eval_iou_best_boxes")
+
+
+NOGC_MAX_K = 100       # the reference counts only the best 100 (sgg_metrics.py:306-308)
+
+
+def nogc_triplets(det, ld, labels, rel_dists, sub_row, obj_row, R, C1, per_row, K, triplets,
+                  sub_rows, obj_rows, scores, count):
+    """The K best no-graph-constraint triplets of one image (csrc/nogc.hip): triplets [K][3],
+    sub_rows / obj_rows [K] int32, scores [K] float32, count [1] int32 = min(K, R * per_row)."""
+    i32 = torch.int32
+    assert det.numel() >= (2 * R - 1) * ld + 5 and labels.numel() >= 2 * R
+    assert rel_dists.numel() == R * C1 and sub_row.numel() >= R and obj_row.numel() >= R
+    assert triplets.numel() == 3 * K and sub_rows.numel() == K and obj_rows.numel() == K
+    assert scores.numel() == K and count.numel() == 1
+    _check(lib().pn_nogc_triplets_f32(_ptr(det), ld, _ptr(labels, torch.int64), _ptr(rel_dists),
+                                      _ptr(sub_row, i32), _ptr(obj_row, i32), R, C1, per_row, K,
+                                      _ptr(triplets, i32), _ptr(sub_rows, i32),
+                                      _ptr(obj_rows, i32), _ptr(scores), _ptr(count, i32),
+                                      _stream()), "pn_nogc_triplets_f32")
 
 
 # ---- panoptic quality (csrc/panoptic_quality.hip) ----
