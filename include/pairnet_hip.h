@@ -1595,6 +1595,37 @@ int pn_groupnorm_act_nhwc_bwd_f32(const float* x, const float* dy, const float* 
                                   int G, float eps, int relu, int accumulate, int64_t x_bstride,
                                   int64_t dy_bstride, void* stream);
 
+/* ---- The training log on the device (csrc/train_log.hip; pair-net_amd/runner.py TrainLog).
+ * Replaces, behind `log_config = dict(interval=50, hooks=[dict(type="TextLoggerHook"), ...])`
+ * (configs/_base_/custom_runtime.py, read by tools/train.py:115-241 through mmcv's runner), mmcv's
+ * `TextLoggerHook` over `LogBuffer.update` / `LogBuffer.average`: there every term of every
+ * iteration is brought to the host (`.item()` in mmdet's `_parse_losses`); here the terms stay on
+ * the device until a window of `interval` iterations is complete.  (mmcv's hook and buffer are
+ * restated from memory, unpinned.)  Entries added at ABI 34.  Vector stores only, no atomics.
+ *
+ * One launch per training step: row `row` of the ring [rows][ld] (32-bit words, ld >= T + 3)
+ * receives
+ *   [0, T)   the step's T scalars: `scalars` is a HOST array of T device pointers to separate
+ *            float32 values (the loss terms, then grad_norm); the launch carries them by value,
+ *            1 <= T <= 32
+ *   [T]      the sum of the scalars i whose bit i of loss_mask is set, 0 + v_a + v_b + ... in
+ *            index order, fp32 (mmdet's `loss`: the terms whose name contains "loss")
+ *   [T + 1]  status0[0] | status1[0] as int32 (either pointer may be NULL: no such word, 0)
+ *   [T + 2]  1.0f where that word is non-zero (the guarded AdamW launch skipped the step), else 0
+ * PN_BAD_ARG before the launch: T outside [1, 32], a NULL among the T pointers, NULL `scalars` or
+ * `ring`, ld < T + 3, row outside [0, rows). */
+int pn_train_log_row_f32(const float* const* scalars, int T, uint32_t loss_mask,
+                         const int32_t* status0, const int32_t* status1, float* ring, int rows,
+                         int ld, int row, void* stream);
+/* One launch per window: from rows [0, n) of that ring, record (T + 4 32-bit words) =
+ *   [0, T]   float32 (((v_0 + v_1) + ...) + v_{n-1}) / n of columns 0 .. T, rows in order
+ *   [T + 1]  int32 the number of rows whose skipped flag is set
+ *   [T + 2]  int32 the OR of the rows' status words        [T + 3]  int32 n
+ * PN_BAD_ARG before the launch: NULL ring / record, T outside [1, 32], ld < T + 3, n outside
+ * [1, rows]. */
+int pn_train_log_window_f32(const float* ring, int rows, int ld, int n, int T, float* record,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@ from .detector import (PSGTr, Result, ResultStreamer, build_detector, load_check
 from .dist import all_gather_triplets, shard_indices  # noqa: F401
 from .evaluation import (PanopticQuality, SceneGraphMetrics, StreamingEvaluator,  # noqa: F401
                          TripletEvaluator)
+from .runner import (EpochRunner, TrainLog, epoch_order, resume, save_checkpoint)  # noqa: F401
 from . import dataset  # noqa: F401  (PSG ground truth: load_psg, ann_info, eval_ground_truth, ...)
 
 __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "CrossHead2",
@@ -43,4 +44,5 @@ __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "Cros
            "TrainPipeline", "AugParams", "HalfSizeMasks", "train_pipeline_cfg", "Mask2FormerLoss",
            "BaselineRelationLoss", "BBoxTailGrad", "BBoxTrainer", "CrossHeadBBoxLoss",
            "PSGTrHead2Loss", "psgtr2_train_cfg", "PSGTr2HeadGrad", "PSGTr2Trainer",
-           "ResNeXtHip", "pairnet_rnext101_vg"]
+           "ResNeXtHip", "pairnet_rnext101_vg",
+           "EpochRunner", "TrainLog", "epoch_order", "resume", "save_checkpoint"]

@@ -744,17 +744,22 @@ class CrossHeadBBox(CrossHead2):
         raise NotImplementedError("CrossHeadBBox has no forward_head (pairnet_bbox_head.py)")
 
     # -------------------------------------------------------------------- loss
+    def loss_object(self):
+        """The `CrossHeadBBoxLoss` behind `loss` (built on first use; it owns SeesawLoss's
+        persistent `cum_samples`, which a checkpoint of a training run carries)."""
+        if self._loss is None:
+            from .bbox_losses import CrossHeadBBoxLoss
+            self._loss = CrossHeadBBoxLoss(self.num_classes, self.num_relations, self.num_rel_query,
+                                           **self._loss_cfg)
+        return self._loss
+
     def loss(self, all_cls_scores, all_bbox_preds, gt_rels_list, gt_bboxes_list, gt_labels_list,
              img_metas, gt_bboxes_ignore=None, **kw):
         """The reference's `CrossHeadBBox.loss` (pairnet_bbox_head.py:362-464): {loss_r_cls,
         loss_sub_cls, loss_obj_cls, loss_match} as 0-dim device tensors from the two dicts
         `forward` returns and the per-image ground truth (bbox_losses.py; `grads={}` receives the
         logit gradients, `device_targets=True` builds the targets without a host wait)."""
-        if self._loss is None:
-            from .bbox_losses import CrossHeadBBoxLoss
-            self._loss = CrossHeadBBoxLoss(self.num_classes, self.num_relations, self.num_rel_query,
-                                           **self._loss_cfg)
-        return self._loss.loss(all_cls_scores, all_bbox_preds, gt_rels_list, gt_bboxes_list,
+        return self.loss_object().loss(all_cls_scores, all_bbox_preds, gt_rels_list, gt_bboxes_list,
                                gt_labels_list, img_metas, gt_bboxes_ignore=gt_bboxes_ignore, **kw)
 
     def forward_train(self, *a, **kw):

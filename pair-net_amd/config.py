@@ -168,8 +168,27 @@ def psgtr2_head_cfg(in_channels=(256, 512, 1024, 2048), num_obj_query=100, num_c
     return cfg
 
 
-def pairnet_r50():
-    """`model` section: PSGTr(ResNet-50, CrossHead2) as the reference configures it."""
+def pairnet_r50(schedule=False):
+    """`model` section: PSGTr(ResNet-50, CrossHead2) as the reference configures it.
+    `schedule=True`: the file-level config instead -- `model` (that section) beside the training
+    sections of configs/mask2former/pairnet.py:342-394 and configs/_base_/custom_runtime.py that
+    `runner.EpochRunner.from_config` reads."""
+    if schedule:
+        keys = ("backbone", "transformer_decoder", "pixel_decoder", "decoder_input_projs")
+        return ConfigDict(
+            model=pairnet_r50(),
+            data=dict(samples_per_gpu=2, workers_per_gpu=2, pin_memory=True),
+            optimizer=dict(type="AdamW", lr=1e-4, weight_decay=1e-4,
+                           paramwise_cfg=dict(
+                               custom_keys={k: dict(lr_mult=0.1, decay_mult=1) for k in keys},
+                               norm_decay_mult=0.0)),
+            optimizer_config=dict(grad_clip=dict(max_norm=0.1, norm_type=2)),
+            lr_config=dict(policy="step", gamma=0.5, step=[5, 10]),
+            runner=dict(type="EpochBasedRunner", max_epochs=15),
+            checkpoint_config=dict(interval=1, max_keep_ckpts=15),
+            log_config=dict(interval=50, hooks=[dict(type="TextLoggerHook")]),
+            auto_scale_lr=dict(enable=True, base_batch_size=8),
+            load_from="pretrain/m2f_r50_coco.pth", resume_from=None)
     return ConfigDict(
         type="PSGTr",
         backbone=dict(type="ResNet", depth=50, num_stages=4, out_indices=(0, 1, 2, 3),

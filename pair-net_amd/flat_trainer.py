@@ -140,6 +140,128 @@ class FlatTrainer:
         if self.backbone is not None and hasattr(self.backbone, "_weights_version"):
             self.backbone._packed_version = self.backbone._weights_version()
 
+    # ---------------------------------------------------------------- the state of a run
+    # which of torch's DEFAULT generators `step()` draws from ("host", "device"); a subclass whose
+    # loss draws its points with `torch.rand` names them here, and they travel with the state
+    DEFAULT_GENERATORS = ()
+
+    def _segment_index(self):
+        return {n: i for i, n in enumerate(self.layout)}
+
+    def _loss_buffers(self):
+        """The loss's persistent buffers as host tensors, under the names its own `state_dict()`
+        uses (SeesawLoss's `cum_samples` of `CrossHead2Loss` / `CrossHeadBBoxLoss`; read back
+        from the device where the device copy is the live one).  The other heads' losses keep
+        nothing between steps."""
+        loss = getattr(self.head, "_loss", None)
+        if loss is None or not hasattr(loss, "state_dict"):
+            return OrderedDict()
+        return OrderedDict((k, v.detach().cpu().clone()) for k, v in loss.state_dict().items())
+
+    def state_dict(self):
+        """Everything of a training run that the model's state dict does not hold, as host
+        tensors and plain Python containers (loads under `torch.load(weights_only=True)`):
+
+        "optimizer": the layout of `torch.optim.AdamW.state_dict()` -- ONE param group per trained
+        parameter, in the order of `self.names` (mmcv's `DefaultOptimizerConstructor` makes one
+        group per parameter when a `paramwise_cfg` is given: restated from memory, UNPINNED like
+        the multiplier rule), each with `lr` (the scheduled rate x the segment's multiplier),
+        `initial_lr`, `weight_decay`, `betas`, `eps`, `amsgrad=False` and `params=[i]`;
+        `state[i] = {"step", "exp_avg", "exp_avg_sq"}` in the parameter's own shape; beside them
+        `"param_names"`, so that a reader can map the entries by name.  Frozen layout names
+        (multipliers 0) are not in it, as they are not in `params`.  (`step` is this trainer's
+        host counter: it advances on a step whose guarded update was skipped on the device too.)
+
+        "trainer": the class name, `steps`, `lr`, `base_lr`, the dropout's seed and subsequence,
+        the `deterministic` / `device_targets` flags, the state of every generator `step()` draws
+        from as uint8 tensors ("drop_path": the host generator of `_drop_path_keep`;
+        "device_default" / "host_default": torch's default generators where the class's
+        `DEFAULT_GENERATORS` names them) and "loss", the loss's persistent buffers.
+
+        The dropout masks (csrc/dropout.hip) and the point draws of the segmentation and triplet
+        losses are functions of (seed, rank, step, site): restoring `steps` restores them, nothing
+        of theirs is stored (tests/test_runner_gpu.py resumes a dropout run bit for bit)."""
+        seg = self._segment_index()
+        lrs, wds = self.seg_lr.cpu().tolist(), self.seg_wd.cpu().tolist()
+        base_lr = getattr(self, "base_lr", self.lr)
+        groups, state = [], {}
+        for i, n in enumerate(self.names):
+            o, shape, k = self.layout[n]
+            s = seg[n]
+            groups.append(dict(lr=self.lr * lrs[s], initial_lr=base_lr * lrs[s],
+                               weight_decay=self.wd * wds[s],
+                               betas=(float(self.betas[0]), float(self.betas[1])),
+                               eps=float(self.eps), amsgrad=False, params=[i]))
+            state[i] = dict(step=torch.tensor(float(self.steps)),
+                            exp_avg=self.flat_m[o:o + k].view(shape).cpu().clone(),
+                            exp_avg_sq=self.flat_v[o:o + k].view(shape).cpu().clone())
+        gens = OrderedDict()
+        if hasattr(self, "_gen"):
+            gens["drop_path"] = self._gen.get_state().clone()
+        if "host" in self.DEFAULT_GENERATORS:
+            gens["host_default"] = torch.get_rng_state().clone()
+        if "device" in self.DEFAULT_GENERATORS:
+            gens["device_default"] = torch.cuda.get_rng_state(self.dev).clone()
+        trainer = {"class": type(self).__name__, "steps": int(self.steps), "lr": float(self.lr),
+                   "base_lr": float(base_lr), "seed": int(getattr(self, "seed", 0)),
+                   "subseq": int(getattr(self, "subseq", 0)),
+                   "deterministic": bool(getattr(self, "deterministic", False)),
+                   "device_targets": bool(getattr(self, "device_targets", False)),
+                   "generators": gens, "loss": self._loss_buffers()}
+        return {"optimizer": {"state": state, "param_groups": groups,
+                              "param_names": list(self.names)},
+                "trainer": trainer}
+
+    def load_state_dict(self, sd):
+        """Restore what `state_dict()` saved: `flat_m` / `flat_v` through views of the same
+        layout, the counters and rates, the generators and the loss buffers.  The PARAMETERS come
+        from the model's state dict, which is loaded before the trainer is built (the trainer's
+        constructor copies them into `flat_p`): this does not touch `flat_p`.  Raises `ValueError`
+        naming the first mismatch (class, parameter names, shapes) before anything is written."""
+        opt, tr = sd["optimizer"], sd["trainer"]
+        if tr["class"] != type(self).__name__:
+            raise ValueError("trainer state of a %s loaded into a %s"
+                             % (tr["class"], type(self).__name__))
+        names = list(opt["param_names"])
+        if names != list(self.names):
+            first = next((i for i, (a, b) in enumerate(zip(names, self.names)) if a != b),
+                         min(len(names), len(self.names)))
+            raise ValueError("parameter names differ at entry %d: the state has %r, the trainer %r "
+                             "(%d against %d names)"
+                             % (first, names[first] if first < len(names) else None,
+                                self.names[first] if first < len(self.names) else None,
+                                len(names), len(self.names)))
+        for i, n in enumerate(self.names):
+            shape = tuple(self.layout[n][1])
+            for key in ("exp_avg", "exp_avg_sq"):
+                got = tuple(opt["state"][i][key].shape)
+                if got != shape:
+                    raise ValueError("%s of %s has shape %s, the trainer's parameter %s"
+                                     % (key, n, got, shape))
+        for flag in ("deterministic", "device_targets"):
+            if bool(tr.get(flag, False)) != bool(getattr(self, flag, False)):
+                raise ValueError("the state was saved with %s=%s, this trainer has %s=%s"
+                                 % (flag, tr.get(flag), flag, getattr(self, flag, False)))
+        for i, n in enumerate(self.names):
+            o, shape, k = self.layout[n]
+            self.flat_m[o:o + k].view(shape).copy_(opt["state"][i]["exp_avg"].to(torch.float32))
+            self.flat_v[o:o + k].view(shape).copy_(opt["state"][i]["exp_avg_sq"].to(torch.float32))
+        self.steps = int(tr["steps"])
+        self.lr, self.base_lr = float(tr["lr"]), float(tr["base_lr"])
+        if hasattr(self, "seed"):
+            self.seed = int(tr["seed"])
+        if hasattr(self, "subseq"):
+            self.subseq = int(tr["subseq"])
+        gens = tr.get("generators", {})
+        if "drop_path" in gens and hasattr(self, "_gen"):
+            self._gen.set_state(gens["drop_path"].cpu())
+        if "host_default" in gens:
+            torch.set_rng_state(gens["host_default"].cpu())
+        if "device_default" in gens:
+            torch.cuda.set_rng_state(gens["device_default"].cpu(), self.dev)
+        if tr.get("loss"):
+            self.head.loss_object().load_state_dict(tr["loss"])
+
     @torch.no_grad()
     @hip.on_device
     def apply_gradients(self, guard=None):

@@ -1563,17 +1563,22 @@ class CrossHead2:
             out.append(dict(nkeep=nkeep, rounds=rounds))
         return out
 
+    def loss_object(self):
+        """The `CrossHead2Loss` behind `loss` (built on first use; it owns SeesawLoss's persistent
+        `cum_samples`, which a checkpoint of a training run carries)."""
+        if self._loss is None:
+            from .losses import CrossHead2Loss
+            self._loss = CrossHead2Loss(self.num_classes, self.num_relations, self.num_obj_query,
+                                        self.num_rel_query, **self._loss_cfg)
+        return self._loss
+
     def loss(self, all_cls_scores, all_mask_preds, gt_rels_list, gt_bboxes_list, gt_labels_list,
              gt_masks_list, img_metas, gt_bboxes_ignore=None, **kw):
         """The reference's `CrossHead2.loss` (pairnet_head.py:419-477), forward values only:
         {loss_r_cls, loss_sub_cls, loss_obj_cls, loss_match} as 0-dim device tensors, from the
         two dicts `forward` returns and the per-image ground truth (losses.py; `point_coords=`
         fixes the sampled mask points, default torch.rand like the reference)."""
-        if self._loss is None:
-            from .losses import CrossHead2Loss
-            self._loss = CrossHead2Loss(self.num_classes, self.num_relations, self.num_obj_query,
-                                        self.num_rel_query, **self._loss_cfg)
-        return self._loss.loss(all_cls_scores, all_mask_preds, gt_rels_list, gt_bboxes_list,
+        return self.loss_object().loss(all_cls_scores, all_mask_preds, gt_rels_list, gt_bboxes_list,
                                gt_labels_list, gt_masks_list, img_metas,
                                gt_bboxes_ignore=gt_bboxes_ignore, **kw)
 

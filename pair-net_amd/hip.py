@@ -269,6 +269,9 @@ _SIGS = {
                                  _i32, _i64] + [_vp] * 7),
     "pn_triplet_heads_bwd_f32": (C.c_int, [_vp] * 14 + [_i32] * 5 + [_vp]),
     "pn_conv2d_grouped_nhwc_f32": (C.c_int, [_vp] * 4 + [_i32] * 9 + [_vp]),
+    "pn_train_log_row_f32": (C.c_int, [C.POINTER(_vp), _i32, C.c_uint32, _vp, _vp, _vp, _i32, _i32,
+                                       _i32, _vp]),
+    "pn_train_log_window_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 34  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
@@ -2215,3 +2218,34 @@ def tri_heads_bwd(dsub, dobj, drel, qn, Wsub, Wobj, Wrel, dqn, dWsub, dbsub, dWo
         _ptr(dsub), _ptr(dobj), _ptr(drel), _ptr(qn), _ptr(Wsub), _ptr(Wobj), _ptr(Wrel), _ptr(dqn),
         _ptr(dWsub), _ptr(dbsub), _ptr(dWobj), _ptr(dbobj), _ptr(dWrel), _ptr(dbrel), N, 256, C1, Cr1,
         int(bool(add)), _stream()), "pn_triplet_heads_bwd_f32")
+
+
+# ---- the training log on the device (csrc/train_log.hip) ----
+LOG_MAX_TERMS = 32      # scalars per step one pn_train_log_row_f32 launch carries by value
+
+
+def train_log_row(scalars, loss_mask, status, ring, row):
+    """ONE launch: the step's T separate 0-dim float32 device scalars, the sum of those whose bit
+    of `loss_mask` is set, the OR of the (up to two, int32) `status` words and the skipped flag
+    -> row `row` of `ring` [rows][>= T + 3] (32-bit words, float32 tensor)."""
+    T = len(scalars)
+    if not 1 <= T <= LOG_MAX_TERMS:
+        raise ValueError("train_log_row: %d scalars (1 .. %d)" % (T, LOG_MAX_TERMS))
+    status = [s for s in status if s is not None]
+    assert len(status) <= 2 and ring.dim() == 2 and ring.stride(1) == 1
+    for v in scalars:
+        assert v.numel() == 1, tuple(v.shape)
+    ptrs = (_vp * T)(*[_ptr(v) for v in scalars])
+    st = [_ptr(s, torch.int32) for s in status] + [None, None]
+    _check(lib().pn_train_log_row_f32(ptrs, T, int(loss_mask) & 0xffffffff, st[0], st[1],
+                                      _ptr(ring), ring.shape[0], ring.stride(0), int(row),
+                                      _stream()), "pn_train_log_row_f32")
+
+
+def train_log_window(ring, n, T, record):
+    """One launch: the means of columns 0 .. T over rows [0, n) of `ring` in row order, the count
+    of skipped rows, the OR of their status words and n -> `record` (>= T + 4 32-bit words)."""
+    assert ring.dim() == 2 and ring.stride(1) == 1 and record.numel() >= T + 4
+    assert record.is_contiguous()
+    _check(lib().pn_train_log_window_f32(_ptr(ring), ring.shape[0], ring.stride(0), int(n), int(T),
+                                         _ptr(record), _stream()), "pn_train_log_window_f32")

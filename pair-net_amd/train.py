@@ -88,6 +88,9 @@ def segment_multipliers(names, frozen, lr_mult=None, decay_mult=None, norm_decay
 
 class TailTrainer(FlatTrainer):
     FROZEN_GROUPS = ("cls",)      # cls_embed / post_norm: no gradient in the reference's graph
+    # `CrossHead2Loss` draws its mask points with `torch.rand(device=)` unless `point_coords=` is
+    # given: the device's default generator is part of a run's state (`FlatTrainer.state_dict`)
+    DEFAULT_GENERATORS = ("device",)
 
     def __init__(self, head, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  max_norm=0.1, norm_decay_mult=0.0, lr_mult=None, group=None,
