@@ -1293,6 +1293,25 @@ typedef struct pn_gemm_s3_desc {
 #define PN_GEMM_S3_TILE96 1   /* force the 96 x 256 tile where the 192 x 256 one would be taken */
 #define PN_GEMM_S3_TILE192 2  /* force the 192 x 256 tile (N >= 512, plain epilogue) whatever its tile count */
 int pn_gemm_s3_f32(const pn_gemm_s3_desc* d, void* stream);
+/* The encoder's FFN as ONE launch (k_gemm_s3_ffn):
+ *   out[m][:] = LayerNorm(relu(X[m][:] W1^T + b1) W2^T + b2 + res[m][:]) * gamma + beta
+ * X [M x K], W1 [F x K], W2 [N x F], res_s3 [M x N] are S3 operands; C / CS / CS_pos / pos as in
+ * pn_gemm_s3_desc.  The F hidden values of a row stay on the chip: a 96-row tile forms them 256
+ * columns at a time in registers, pre-split, and hands them to the second GEMM through LDS.
+ * Every output is bit for bit that of the two pn_gemm_s3_f32 calls (act = ReLU -> CS, then res_s3 +
+ * LayerNorm) it replaces.  Handled: K == 256, N == 256, F % 256 == 0, act == 1 (ReLU), gamma and
+ * beta given; anything else returns PN_BAD_ARG without launching. */
+typedef struct pn_gemm_s3_ffn_desc {
+  const void* X;  const void* W1;  const float* b1;    /* b1 [F] or NULL */
+  const void* W2; const float* b2;                      /* b2 [N] or NULL */
+  int32_t M, N, K, F;
+  int32_t act;                                          /* pn_gemm_s3_desc's codes; 1 (ReLU) only */
+  float* C;       int64_t ldc;
+  void* CS;
+  void* CS_pos;   const float* pos;  int32_t pos_rows;
+  const void* res_s3;  const float* gamma;  const float* beta;  float eps;
+} pn_gemm_s3_ffn_desc;
+int pn_gemm_s3_ffn_f32(const pn_gemm_s3_ffn_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * The Mask2Former segmentation losses (csrc/seg_loss.hip; pair-net_amd/seg_losses.py drives them):

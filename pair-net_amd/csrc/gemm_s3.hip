@@ -166,6 +166,156 @@ __device__ __forceinline__ void s3_block_epilogue(const f32x16& acc, const s3_ar
   }
 }
 
+// The row epilogue of a 96-row x 256-column tile: out = LayerNorm(acc + bias + residual), written
+// as fp32 rows, as S3 pieces and / or as the S3 pieces of out + pos.  acc[m] is the TRANSPOSED
+// 32 x 32 block of row block rb0 + m and columns n0 .. n0 + 31 (this wave's); `smem` is the
+// workgroup's ring memory, free once every wave has passed the function's first barrier.
+__device__ __forceinline__ void s3_ln_epilogue(const f32x16 (&acc)[3], const s3_args& p, uint4* smem,
+                                               int rb0, int n0, int wave, int lane) {
+  constexpr int MB = 3;
+  const int M = p.M, RB = (M + 31) >> 5;
+  const int li = lane & 31, lh = lane >> 5;
+  const bool cols_ok = n0 < p.N;                     // N % 32 == 0: a wave is all in or all out
+  // v[m][j][i]: row (rb0 + m) * 32 + li, column n0 + 16 j + 8 lh + i  (after the swaps)
+  float v[MB][2][8];
+#pragma unroll
+  for (int m = 0; m < MB; ++m)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        // lower lanes hold columns 16j + {0-3, 8-11}, upper lanes 16j + {4-7, 12-15}: exchange the
+        // lower lanes' second quad with the upper lanes' first quad
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[m][8 * j + i]),
+                                                         __float_as_uint(acc[m][8 * j + 4 + i]), false, false);
+        v[m][j][i] = __uint_as_float(sw[0]);
+        v[m][j][4 + i] = __uint_as_float(sw[1]);
+      }
+  if (p.bias && cols_ok) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const float4 b0 = ld4(p.bias + n0 + 16 * j + 8 * lh), b1 = ld4(p.bias + n0 + 16 * j + 8 * lh + 4);
+      const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+      for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[m][j][i] += bb[i];
+    }
+  }
+  if (p.relu) {
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[m][j][i] = fmaxf(v[m][j][i], 0.f);
+  }
+  {
+#pragma clang fp contract(off)
+    // residual: the exact fp32 values of an S3 operand [M x 256] (three planes summed)
+    if (p.RES) {
+#pragma unroll
+      for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const uint4* in = p.RES + ((int64_t)min(rb0 + m, RB - 1) * 16 + wave * 2 + j) * 192 + lane;
+          s3_frag q0, q1, q2;
+          q0.u = in[0]; q1.u = in[64]; q2.u = in[128];
+          float r[8];
+          s3_join8(q0, q1, q2, r);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) v[m][j][i] += r[i];
+        }
+    }
+    // two-pass moments over the 256 columns of a row: 16 values in this lane, 16 in lane ^ 32, the
+    // rest in the other 7 waves (through LDS, over the rings: every ring read is behind a barrier)
+    float* red = (float*)smem;                       // [2][8 waves][96 rows]
+    __syncthreads();
+    float s1[MB];
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += v[m][j][i];
+      s += __shfl_xor(s, 32, 64);
+      if (lh == 0) red[wave * 96 + m * 32 + li] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      float s = 0.f;
+#pragma unroll
+      for (int w = 0; w < 8; ++w) s += red[w * 96 + m * 32 + li];
+      s1[m] = s * (1.f / 256.f);
+    }
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { v[m][j][i] -= s1[m]; s += v[m][j][i] * v[m][j][i]; }
+      s += __shfl_xor(s, 32, 64);
+      if (lh == 0) red[768 + wave * 96 + m * 32 + li] = s;
+    }
+    __syncthreads();
+    float g[2][8], be[2][8];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const float4 g0 = ld4(p.gamma + n0 + 16 * j + 8 * lh), g1 = ld4(p.gamma + n0 + 16 * j + 8 * lh + 4);
+      const float4 e0 = ld4(p.beta + n0 + 16 * j + 8 * lh), e1 = ld4(p.beta + n0 + 16 * j + 8 * lh + 4);
+      g[j][0] = g0.x; g[j][1] = g0.y; g[j][2] = g0.z; g[j][3] = g0.w; g[j][4] = g1.x; g[j][5] = g1.y; g[j][6] = g1.z; g[j][7] = g1.w;
+      be[j][0] = e0.x; be[j][1] = e0.y; be[j][2] = e0.z; be[j][3] = e0.w; be[j][4] = e1.x; be[j][5] = e1.y; be[j][6] = e1.z; be[j][7] = e1.w;
+    }
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      float s = 0.f;
+#pragma unroll
+      for (int w = 0; w < 8; ++w) s += red[768 + w * 96 + m * 32 + li];
+      const float rstd = 1.f / sqrtf(s * (1.f / 256.f) + p.eps);
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[m][j][i] = (v[m][j][i] * rstd) * g[j][i] + be[j][i];
+    }
+  }
+  if (!cols_ok) return;
+  const int KBo = p.nout >> 4;
+#pragma unroll
+  for (int m = 0; m < MB; ++m) {
+    if (rb0 + m >= RB) break;
+    const int row = (rb0 + m) * 32 + li;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (p.C && row < M) {
+        float* c = p.C + (int64_t)row * p.ldc + n0 + 16 * j + 8 * lh;
+        st4(c, make_float4(v[m][j][0], v[m][j][1], v[m][j][2], v[m][j][3]));
+        st4(c + 4, make_float4(v[m][j][4], v[m][j][5], v[m][j][6], v[m][j][7]));
+      }
+      const int64_t piece = ((int64_t)(rb0 + m) * KBo + (n0 >> 4) + j) * 192 + lane;
+      if (p.CS) {
+        s3_frag q0, q1, q2;
+        s3_split8(v[m][j], q0, q1, q2);
+        uint4* o = p.CS + piece;
+        o[0] = q0.u; o[64] = q1.u; o[128] = q2.u;
+      }
+      if (p.CSP) {
+        // the next layer's query operand: split(out + pos[row % pos_rows])
+        const float* pp = p.pos + pos8_offset(min(row, M - 1) % p.pos_rows, n0 + 16 * j + 8 * lh, p.nout);
+        const float4 p0 = ld4(pp), p1 = ld4(pp + 4);
+        const float w[8] = {v[m][j][0] + p0.x, v[m][j][1] + p0.y, v[m][j][2] + p0.z, v[m][j][3] + p0.w,
+                            v[m][j][4] + p1.x, v[m][j][5] + p1.y, v[m][j][6] + p1.z, v[m][j][7] + p1.w};
+        s3_frag q0, q1, q2;
+        s3_split8(w, q0, q1, q2);
+        uint4* o = p.CSP + piece;
+        o[0] = q0.u; o[64] = q1.u; o[128] = q2.u;
+      }
+    }
+  }
+}
+
 // LN: the row epilogue out = LayerNorm(acc + bias + residual) (N == 256, one column tile)
 #ifndef S3_LATE_B
 #define S3_LATE_B 0
@@ -339,146 +489,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_s3(const s3_args p) {
     }
     return;
   }
-  const int li = lane & 31, lh = lane >> 5;
-  const bool cols_ok = n0 < N;                       // N % 32 == 0: a wave is all in or all out
-  // v[m][j][i]: row (rb0 + m) * 32 + li, column n0 + 16 j + 8 lh + i  (after the swaps)
-  float v[MB][2][8];
-#pragma unroll
-  for (int m = 0; m < MB; ++m)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        // lower lanes hold columns 16j + {0-3, 8-11}, upper lanes 16j + {4-7, 12-15}: exchange the
-        // lower lanes' second quad with the upper lanes' first quad
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[m][8 * j + i]),
-                                                         __float_as_uint(acc[m][8 * j + 4 + i]), false, false);
-        v[m][j][i] = __uint_as_float(sw[0]);
-        v[m][j][4 + i] = __uint_as_float(sw[1]);
-      }
-  if (p.bias && cols_ok) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const float4 b0 = ld4(p.bias + n0 + 16 * j + 8 * lh), b1 = ld4(p.bias + n0 + 16 * j + 8 * lh + 4);
-      const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-      for (int m = 0; m < MB; ++m)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[m][j][i] += bb[i];
-    }
-  }
-  if (p.relu) {
-#pragma unroll
-    for (int m = 0; m < MB; ++m)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[m][j][i] = fmaxf(v[m][j][i], 0.f);
-  }
-  if (LN) {
-#pragma clang fp contract(off)
-    // residual: the exact fp32 values of an S3 operand [M x 256] (three planes summed)
-    if (p.RES) {
-#pragma unroll
-      for (int m = 0; m < MB; ++m)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const uint4* in = p.RES + ((int64_t)min(rb0 + m, RB - 1) * 16 + wave * 2 + j) * 192 + lane;
-          s3_frag q0, q1, q2;
-          q0.u = in[0]; q1.u = in[64]; q2.u = in[128];
-          float r[8];
-          s3_join8(q0, q1, q2, r);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) v[m][j][i] += r[i];
-        }
-    }
-    // two-pass moments over the 256 columns of a row: 16 values in this lane, 16 in lane ^ 32, the
-    // rest in the other 7 waves (through LDS, over the rings: every ring read is behind a barrier)
-    float* red = (float*)smem;                       // [2][8 waves][96 rows]
-    __syncthreads();
-    float s1[MB];
-#pragma unroll
-    for (int m = 0; m < MB; ++m) {
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s += v[m][j][i];
-      s += __shfl_xor(s, 32, 64);
-      if (lh == 0) red[wave * 96 + m * 32 + li] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int m = 0; m < MB; ++m) {
-      float s = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) s += red[w * 96 + m * 32 + li];
-      s1[m] = s * (1.f / 256.f);
-    }
-#pragma unroll
-    for (int m = 0; m < MB; ++m) {
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { v[m][j][i] -= s1[m]; s += v[m][j][i] * v[m][j][i]; }
-      s += __shfl_xor(s, 32, 64);
-      if (lh == 0) red[768 + wave * 96 + m * 32 + li] = s;
-    }
-    __syncthreads();
-    float g[2][8], be[2][8];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const float4 g0 = ld4(p.gamma + n0 + 16 * j + 8 * lh), g1 = ld4(p.gamma + n0 + 16 * j + 8 * lh + 4);
-      const float4 e0 = ld4(p.beta + n0 + 16 * j + 8 * lh), e1 = ld4(p.beta + n0 + 16 * j + 8 * lh + 4);
-      g[j][0] = g0.x; g[j][1] = g0.y; g[j][2] = g0.z; g[j][3] = g0.w; g[j][4] = g1.x; g[j][5] = g1.y; g[j][6] = g1.z; g[j][7] = g1.w;
-      be[j][0] = e0.x; be[j][1] = e0.y; be[j][2] = e0.z; be[j][3] = e0.w; be[j][4] = e1.x; be[j][5] = e1.y; be[j][6] = e1.z; be[j][7] = e1.w;
-    }
-#pragma unroll
-    for (int m = 0; m < MB; ++m) {
-      float s = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) s += red[768 + w * 96 + m * 32 + li];
-      const float rstd = 1.f / sqrtf(s * (1.f / 256.f) + p.eps);
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[m][j][i] = (v[m][j][i] * rstd) * g[j][i] + be[j][i];
-    }
-  }
-  if (!cols_ok) return;
-  const int KBo = p.nout >> 4;
-#pragma unroll
-  for (int m = 0; m < MB; ++m) {
-    if (rb0 + m >= RB) break;
-    const int row = (rb0 + m) * 32 + li;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (p.C && row < M) {
-        float* c = p.C + (int64_t)row * p.ldc + n0 + 16 * j + 8 * lh;
-        st4(c, make_float4(v[m][j][0], v[m][j][1], v[m][j][2], v[m][j][3]));
-        st4(c + 4, make_float4(v[m][j][4], v[m][j][5], v[m][j][6], v[m][j][7]));
-      }
-      const int64_t piece = ((int64_t)(rb0 + m) * KBo + (n0 >> 4) + j) * 192 + lane;
-      if (p.CS) {
-        s3_frag q0, q1, q2;
-        s3_split8(v[m][j], q0, q1, q2);
-        uint4* o = p.CS + piece;
-        o[0] = q0.u; o[64] = q1.u; o[128] = q2.u;
-      }
-      if (p.CSP) {
-        // the next layer's query operand: split(out + pos[row % pos_rows])
-        const float* pp = p.pos + pos8_offset(min(row, M - 1) % p.pos_rows, n0 + 16 * j + 8 * lh, p.nout);
-        const float4 p0 = ld4(pp), p1 = ld4(pp + 4);
-        const float w[8] = {v[m][j][0] + p0.x, v[m][j][1] + p0.y, v[m][j][2] + p0.z, v[m][j][3] + p0.w,
-                            v[m][j][4] + p1.x, v[m][j][5] + p1.y, v[m][j][6] + p1.z, v[m][j][7] + p1.w};
-        s3_frag q0, q1, q2;
-        s3_split8(w, q0, q1, q2);
-        uint4* o = p.CSP + piece;
-        o[0] = q0.u; o[64] = q1.u; o[128] = q2.u;
-      }
-    }
-  }
+  s3_ln_epilogue(acc, p, smem, rb0, n0, wave, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -622,6 +633,254 @@ __global__ __launch_bounds__(512, 1) void k_gemm_s3_wide(const s3_args p) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The encoder's FFN in one launch: out = LayerNorm(relu(X W1^T + b1) W2^T + b2 + res), the hidden
+// rows never leaving the chip.  k_gemm_s3's geometry (96 whole rows per workgroup, 8 waves, two
+// groups alternating READ / MMA phases, the same rings); the hidden dimension F is walked in
+// chunks of 256 columns, 16 stages each:
+//   stages 0-7  (FFN-1): the chunk's 96 x 256 block of X W1^T over K = 256 -- X and the chunk's
+//                W1 rows by LDS-DMA, exactly k_gemm_s3<false>'s loop; wave w ends with columns
+//                32 w .. 32 w + 31 of the block, i.e. with the 32-deep k-stage w of FFN-2's
+//                activation operand, whose S3 pieces (bias, ReLU, split: s3_block_epilogue's
+//                values) it forms in registers -- 18 KiB per wave, one A-ring stage;
+//   stages 8-15 (FFN-2): stage 8 + s multiplies wave s's pieces, written by that wave into the
+//                stage's A-ring slot at the lane-linear positions the DMA would have used, with
+//                W2's k-stage (8 chunk + s) by LDS-DMA; three accumulators per wave persist
+//                across the chunks.
+// FFN-1's products and FFN-2's (ascending k, six products per 16-deep step in k_gemm_s3's order)
+// are those of the two-launch form, so every output is bit for bit the same.
+// Between stages 7 and 8 each group spends one phase on the FFN-1 epilogue ("E") beside the other
+// group's MMA(7) / READ(8); everything else streams: the next chunk's X and W1 stages are issued
+// during stages 14-15.  Ring rules as in k_gemm_s3; for the register-written pieces: a piece is
+// written (and lgkmcnt(0) waited) at least one barrier before its first reader's READ phase and
+// at least two phases after the last read of the slot's previous stage.  With phase numbers
+// G0 READ(g) = 2g, G0 MMA(g) = G1 READ(g) = 2g + 1, G1 MMA(g) = 2g + 2 (g >= 8; one less before
+// the E phases, G0's E = 15, G1's = 16):
+//   waves 0, 1 write stages 8, 9 in phase 15 (slots last read in phases 10, 12; first read 16, 18)
+//   wave 2 + i writes stage 10 + i in its group's MMA(8 + i): i = 0, 1 in phase 17 + 2i, i >= 2 in
+//   phase 18 + 2i (slot last read in phase 15 + 2i by G1's READ(7 + i); first read in phase 20 + 2i)
+__global__ __launch_bounds__(512, 1) void k_gemm_s3_ffn(const s3_args p, const uint4* __restrict__ W1,
+                                                        const float* __restrict__ b1) {
+  constexpr int MB = 3;
+  constexpr int AH = 9 * 64, AST = 2 * AH;           // uint4 per A half (16-deep) / A stage
+  constexpr int BH = 24 * 64, BST = 2 * BH;          // uint4 per W half / W stage
+  constexpr int BRING = 3 * AST;
+  constexpr int CHUNK1 = 8 * 16 * 192;               // uint4 per 256 rows of W1 (K = 256)
+  __shared__ __attribute__((aligned(1024))) uint4 smem[3 * AST + 2 * BST];   // 150 KiB
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = wave >> 2, wq = wave & 3;
+  const int M = p.M, KB2 = p.K >> 4, NC = p.K >> 8;  // p.K = F, FFN-2's reduction length
+  const int RB = (M + 31) >> 5, mt = (RB + MB - 1) / MB;
+  const int rb0 = xcd_tile_index(blockIdx.x, mt) * MB;
+
+  // LDS-DMA pieces of this wave: per stage the six of W that are its OWN column block's (3 planes
+  // x 2 halves: the fragments it reads itself), per half stage of X the three planes of row block
+  // wq (waves 0-2 of each group).  One wave-uniform base per operand, the pieces at constant
+  // offsets from it, the lane added last.
+  const int cb = grp * 4 + wq;
+  const uint4* gW1 = W1 + cb * 16 * 192;
+  const uint4* gW2 = p.W + (int64_t)cb * KB2 * 192;
+  const uint4* gX = p.A + (int64_t)min(rb0 + wq, RB - 1) * 16 * 192;
+  const int lW = cb * 3 * 64, lX = wq * 3 * 64;
+  const bool xw = wq < 3;
+  const unsigned ul = lane;
+  auto issueW1 = [&](int c, int u) {                 // W1 rows of chunk c, stage u
+    const uint4* g = gW1 + (int64_t)c * CHUNK1 + u * 384;
+    const int base = BRING + (u & 1) * BST + lW;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) s3_glds16(g + (h * 192 + q * 64) + ul, &smem[base + h * BH + q * 64]);
+  };
+  auto issueW2 = [&](int c, int s) {                 // W2's k-stage 8 c + s
+    const uint4* g = gW2 + (c * 8 + s) * 384;
+    const int base = BRING + (s & 1) * BST + lW;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) s3_glds16(g + (h * 192 + q * 64) + ul, &smem[base + h * BH + q * 64]);
+  };
+  auto issueA = [&](int u, int as, int half) {       // one 16-deep half of X's stage u into slot as
+    if (!xw) return;
+    const uint4* g = gX + (2 * u + half) * 192;
+    const int base = as * AST + half * AH + lX;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) s3_glds16(g + q * 64 + ul, &smem[base + q * 64]);
+  };
+  s3_frag a[2][MB][3], b[2][3];
+  const int bfrag = (grp * 4 + wq) * 3 * 64 + lane;
+  auto read = [&](int ws, int as) {
+    const uint4* pa = smem + as * AST + lane;
+    const uint4* pb = smem + BRING + ws * BST + bfrag;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) a[h][m][q].u = pa[h * AH + (m * 3 + q) * 64];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) b[h][q].u = pb[h * BH + q * 64];
+    }
+  };
+  auto mma = [&](f32x16 (&acc)[MB]) {                // k_gemm_s3's order
+    constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int q = 0; q < 6; ++q)
+#pragma unroll
+        for (int m = 0; m < MB; ++m)
+          acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[h][PB[q]].v, a[h][m][PA[q]].v, acc[m], 0, 0, 0);
+  };
+  auto bar = [&] {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto drain_bar = [&] {                             // vmcnt(0) (LDS-DMA) and lgkmcnt(0) (ds_write)
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0x0070);
+    bar();
+  };
+  f32x16 acc1[MB], acc2[MB];
+#pragma unroll
+  for (int m = 0; m < MB; ++m)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc2[m][r] = 0.f;
+  // this wave's 96 x 32 piece of the chunk's hidden block: [row block][16-deep half][plane]
+  s3_frag pc[MB][2][3];
+  auto make_pieces = [&](int c) {                    // s3_block_epilogue's values
+    const int lh = lane >> 5;
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc1[m][8 * j + i]),
+                                                           __float_as_uint(acc1[m][8 * j + 4 + i]), false, false);
+          v[i] = __uint_as_float(sw[0]);
+          v[4 + i] = __uint_as_float(sw[1]);
+        }
+        if (b1) {
+          const float* bp = b1 + c * 256 + wave * 32 + 16 * j + 8 * lh;
+          const float4 b0 = ld4(bp), b1v = ld4(bp + 4);
+          v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w; v[4] += b1v.x; v[5] += b1v.y; v[6] += b1v.z; v[7] += b1v.w;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i], 0.f);
+        s3_split8(v, pc[m][j][0], pc[m][j][1], pc[m][j][2]);
+        // (held PACKED until written: left alone the compiler keeps one register per bf16 and
+        // packs at the ds_write, twice the registers over the FFN-2 stages in between)
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+          asm volatile("" : "+v"(pc[m][j][q].u.x), "+v"(pc[m][j][q].u.y), "+v"(pc[m][j][q].u.z), "+v"(pc[m][j][q].u.w));
+      }
+    }
+  };
+  auto write_pieces = [&](int as) {                  // where issueA would have put an X stage
+    uint4* d = smem + as * AST + lane;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) d[j * AH + (m * 3 + q) * 64] = pc[m][j][q].u;
+  };
+  auto zero1 = [&] {                                 // (acc1 is dead from E to the next chunk)
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc1[m][r] = 0.f;
+  };
+
+  // ---- prologue: stage 0 whole (every wave its W1 pieces, X's halves one per group), and X's
+  // second half of stage 1 ----
+  issueW1(0, 0);
+  issueA(0, 0, grp);
+  if (grp == 1) issueA(1, 1, 1);
+  drain_bar();
+  int as = 0;                                        // A-ring slot of the current stage
+  if (grp == 0) {
+    for (int c = 0; c < NC; ++c) {
+      zero1();
+#pragma unroll 1
+      for (int u = 0; u < 8; ++u) {
+        const int as1 = as == 2 ? 0 : as + 1;
+        __builtin_amdgcn_s_setprio(1);
+        read(u & 1, as);
+        if (u < 7) { issueW1(c, u + 1); issueA(u + 1, as1, 0); }
+        else issueW2(c, 0);
+        __builtin_amdgcn_s_setprio(0);
+        bar();
+        mma(acc1);
+        drain_bar();
+        as = as1;
+      }
+      // E: `as` is stage 8's slot
+      make_pieces(c);
+      if (wave < 2) write_pieces(wave == 0 ? as : (as == 2 ? 0 : as + 1));
+      drain_bar();
+#pragma unroll 1
+      for (int s = 0; s < 8; ++s) {
+        const int as1 = as == 2 ? 0 : as + 1;
+        __builtin_amdgcn_s_setprio(1);
+        read(s & 1, as);
+        if (s < 7) issueW2(c, s + 1);
+        else if (c + 1 < NC) { issueW1(c + 1, 0); issueA(0, as1, 0); }
+        __builtin_amdgcn_s_setprio(0);
+        bar();
+        mma(acc2);
+        if (wave == s + 2) write_pieces(as == 0 ? 2 : as - 1);      // stage 8 + s + 2's slot
+        drain_bar();
+        as = as1;
+      }
+    }
+  } else {
+    bar();
+    for (int c = 0; c < NC; ++c) {
+      zero1();
+#pragma unroll 1
+      for (int u = 0; u < 8; ++u) {
+        const int as2 = as == 0 ? 2 : as - 1;        // (stage + 2) % 3
+        __builtin_amdgcn_s_setprio(1);
+        read(u & 1, as);
+        if (u < 7) issueW1(c, u + 1);
+        else issueW2(c, 0);
+        if (u + 2 < 8) issueA(u + 2, as2, 1);
+        __builtin_amdgcn_s_setprio(0);
+        bar();
+        mma(acc1);
+        drain_bar();
+        as = as == 2 ? 0 : as + 1;
+      }
+      // E
+      make_pieces(c);
+      bar();
+#pragma unroll 1
+      for (int s = 0; s < 8; ++s) {
+        const int as2 = as == 0 ? 2 : as - 1;
+        const bool more = c + 1 < NC;
+        __builtin_amdgcn_s_setprio(1);
+        read(s & 1, as);
+        if (s < 7) issueW2(c, s + 1);
+        else if (more) issueW1(c + 1, 0);
+        if (s >= 6 && more) issueA(s - 6, as2, 1);
+        __builtin_amdgcn_s_setprio(0);
+        bar();
+        mma(acc2);
+        if (wave == s + 2) write_pieces(as2);        // stage 8 + s + 2's slot
+        if (more || s < 7) drain_bar();
+        as = as == 2 ? 0 : as + 1;
+      }
+    }
+  }
+  s3_ln_epilogue(acc2, p, smem, rb0, wave * 32, wave, lane);
+}
+
 // Leftover columns (N % 256 of at most 64, e.g. the last 32 of the encoder's 544-column
 // [value | offsets | logits] projection): one wave per (row block, column block), operands straight
 // to registers -- nothing is shared, 0.4 GFLOP, latency-bound and short.
@@ -679,6 +938,27 @@ extern "C" int pn_s3_join_f32(const void* S, float* X, int64_t ld, int rows, int
   const int64_t np = (int64_t)((rows + 31) / 32) * (K / 16);
   k_s3_join<<<dim3((unsigned)((np + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
       (const uint4*)S, X, ld, rows, K);
+  return PN_LAUNCH_CHECK();
+}
+
+extern "C" int pn_gemm_s3_ffn_f32(const pn_gemm_s3_ffn_desc* d, void* stream) {
+  if (!d || !d->X || !d->W1 || !d->W2 || d->M <= 0) return PN_BAD_ARG;
+  if (d->K != 256 || d->N != 256 || d->F <= 0 || d->F % 256) return PN_BAD_ARG;
+  if (d->act != 1) return PN_BAD_ARG;                       // ReLU only
+  if (!d->gamma || !d->beta) return PN_BAD_ARG;             // the row epilogue is the LayerNorm one
+  if (!d->C && !d->CS && !d->CS_pos) return PN_BAD_ARG;
+  if (d->C && (d->ldc % 4 || d->ldc < d->N)) return PN_BAD_ARG;
+  if (d->CS_pos && (!d->pos || d->pos_rows <= 0)) return PN_BAD_ARG;
+  s3_args a;
+  a.A = (const uint4*)d->X; a.A2 = nullptr; a.a2_from_tile = 0;
+  a.W = (const uint4*)d->W2; a.bias = d->b2;
+  a.C = d->C; a.ldc = d->ldc; a.CS = (uint4*)d->CS; a.CSP = (uint4*)d->CS_pos;
+  a.RES = (const uint4*)d->res_s3; a.gamma = d->gamma; a.beta = d->beta; a.pos = d->pos;
+  a.pos_rows = d->pos_rows; a.eps = d->eps;
+  a.M = d->M; a.N = d->N; a.K = d->F; a.relu = 0; a.nout = d->N;
+  a.res = nullptr; a.ldres = 0;
+  const int RB = (d->M + 31) / 32, mt = (RB + 2) / 3;
+  k_gemm_s3_ffn<<<dim3(mt), dim3(512), 0, (hipStream_t)stream>>>(a, (const uint4*)d->W1, d->b1);
   return PN_LAUNCH_CHECK();
 }
 

@@ -177,6 +177,11 @@ class CrossHead2:
         # (pn_mask_stencil_gather_gemm_f32): stage A no longer copies them into pl.MFs, three
         # launches and 90 MB of writes per 800 x 1333 image; bit-identical, False restores the copies
         self.gather_mask_stencil = True
+        # the encoder layers' FFN (Linear-ReLU-Linear + identity + norms.1) as ONE launch on the
+        # bf16x3 path (pn_gemm_s3_ffn_f32): the 1024 hidden values of a row go from FFN-1's
+        # registers through LDS into FFN-2's MFMAs instead of through pl.HS, 270 MB of traffic per
+        # layer at 800 x 1333; bit-identical, 0 restores the two launches (labnotes R34)
+        self.fuse_encoder_ffn = 1
         # lateral GroupNorm and the top-down upsample-add as one pass over the stride-4 map
         # (pn_groupnorm_upadd_nhwc_f32) instead of two, bit-identical.  Off by default: 78 against
         # 90 us stand-alone, but no difference in the pipelined step beyond its run-to-run spread
@@ -830,6 +835,8 @@ class CrossHead2:
         M, F = B * SN, self.enc_ffn
         X2 = pl.X.view(-1, 256)
         pos8 = (pl.enc_pos8, SN)
+        # the one-launch FFN handles a hidden width that is a multiple of 256 (the config's 1024)
+        fuse_ffn = bool(getattr(self, "fuse_encoder_ffn", 0)) and F % 256 == 0
         hip.s3_split(X2, pl.XS)
         hip.s3_split(X2, pl.XPS, add=pl.enc_pos)
         for i in range(self.num_enc_layers):
@@ -846,13 +853,19 @@ class CrossHead2:
             hip.gemm_s3(pl.SS, w[a + "output_proj.weight.s3"], M, 256, 256,
                         bias=w[a + "output_proj.bias"], out_s3=pl.X1S, res_s3=pl.XS,
                         gamma=w[p + "norms.0.weight"], beta=w[p + "norms.0.bias"])
+            tail = dict(res_s3=pl.X1S, gamma=w[p + "norms.1.weight"], beta=w[p + "norms.1.bias"],
+                        out=X2 if last else None, out_s3=None if last else pl.XS,
+                        out_s3_pos=None if last else pl.XPS, pos=pos8)
+            if fuse_ffn:                 # (pl.HS stays carved and is not written)
+                hip.gemm_s3_ffn(pl.X1S, w[p + "ffns.0.layers.0.0.weight.s3"],
+                                w[p + "ffns.0.layers.1.weight.s3"], M, 256, 256, F,
+                                b1=w[p + "ffns.0.layers.0.0.bias"],
+                                b2=w[p + "ffns.0.layers.1.bias"], **tail)
+                continue
             hip.gemm_s3(pl.X1S, w[p + "ffns.0.layers.0.0.weight.s3"], M, F, 256,
                         bias=w[p + "ffns.0.layers.0.0.bias"], relu=True, out_s3=pl.HS)
             hip.gemm_s3(pl.HS, w[p + "ffns.0.layers.1.weight.s3"], M, 256, F,
-                        bias=w[p + "ffns.0.layers.1.bias"], res_s3=pl.X1S,
-                        gamma=w[p + "norms.1.weight"], beta=w[p + "norms.1.bias"],
-                        out=X2 if last else None, out_s3=None if last else pl.XS,
-                        out_s3_pos=None if last else pl.XPS, pos=pos8)
+                        bias=w[p + "ffns.0.layers.1.bias"], **tail)
 
     def _mlp3(self, prefix, src, dst, pl):
         """Linear-ReLU-Linear-ReLU-Linear (`mask_embed`-style heads) via pl.m1 / pl.m2."""
@@ -1157,7 +1170,7 @@ class CrossHead2:
         cfg = (self.exact_mask_order, self.conv_algo, self.fuse_ppn_front, self.grid_reserve,
                tuple(self.enc_fused_ln), self.group_input_convs,
                getattr(self, "fuse_mask_pack", True), self.gemm_arithmetic, self.msda_s3_out,
-               self._fused_pair_masks(),
+               self._fused_pair_masks(), bool(getattr(self, "fuse_encoder_ffn", 0)),
                getattr(self, "gather_mask_stencil", True), getattr(self, "fuse_lateral_upadd", False))
         if pl.graph_cfg != cfg:          # a captured graph bakes these switches in
             pl.graph_a = pl.graph_b = None

@@ -51,12 +51,22 @@ class GemmS3Desc(C.Structure):
                 ("act", _i32), ("res", _vp), ("ldres", _i64)]
 
 
+class GemmS3FfnDesc(C.Structure):
+    _fields_ = [("X", _vp), ("W1", _vp), ("b1", _vp), ("W2", _vp), ("b2", _vp),
+                ("M", _i32), ("N", _i32), ("K", _i32), ("F", _i32), ("act", _i32),
+                ("C", _vp), ("ldc", _i64),
+                ("CS", _vp),
+                ("CS_pos", _vp), ("pos", _vp), ("pos_rows", _i32),
+                ("res_s3", _vp), ("gamma", _vp), ("beta", _vp), ("eps", _f32)]
+
+
 _SIGS = {
     "pn_abi_version": (C.c_int, []),
     "pn_s3_bytes": (_i64, [_i32, _i32]),
     "pn_s3_split_f32": (C.c_int, [_vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp]),
     "pn_s3_join_f32": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),
     "pn_gemm_s3_f32": (C.c_int, [C.POINTER(GemmS3Desc), _vp]),
+    "pn_gemm_s3_ffn_f32": (C.c_int, [C.POINTER(GemmS3FfnDesc), _vp]),
     "pn_gemm_f32": (C.c_int, [C.POINTER(GemmDesc), _vp]),
     "pn_gemm_variant": (C.c_int, [C.POINTER(GemmDesc)]),
     "pn_gemm_grid_size": (C.c_int, [C.POINTER(GemmDesc)]),
@@ -742,6 +752,34 @@ def gemm_s3(a, w, M, N, K, *, bias=None, relu=False, out=None, out_s3=None, out_
     name = "k_gemm_s3<ln>" if gamma is not None else "k_gemm_s3"    # (both tile forms)
     _check(_launch(name, 2.0 * M * N * K, nbytes, lambda: lib().pn_gemm_s3_f32(C.byref(d), _stream()),
                    meta=(M, N, K, 1, False)), "pn_gemm_s3_f32")
+
+
+def gemm_s3_ffn(x, w1, w2, M, N, K, F, *, b1=None, b2=None, res_s3=None, gamma=None, beta=None,
+                eps=1e-5, out=None, out_s3=None, out_s3_pos=None, pos=None, gelu=False):
+    """The encoder's FFN as one launch (csrc/gemm_s3.hip, k_gemm_s3_ffn):
+    LayerNorm(relu(x @ w1.T + b1) @ w2.T + b2 + res) * gamma + beta, bit for bit the
+    gemm_s3(relu=True, out_s3=hidden) -> gemm_s3(hidden, res_s3=, gamma=, beta=) pair without the
+    hidden rows in memory.  x [M x K], w1 [F x K], w2 [N x F], res_s3, out_s3, out_s3_pos are S3
+    buffers; out is 2-D fp32 rows.  K == N == 256, F % 256 == 0, ReLU and a LayerNorm only: the
+    library refuses the rest."""
+    d = GemmS3FfnDesc()
+    d.X, d.W1, d.b1, d.W2, d.b2 = _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2)
+    d.M, d.N, d.K, d.F, d.act = M, N, K, F, 2 if gelu else 1
+    if out is not None:
+        Mo, ldc = _rowmajor(out)
+        assert Mo == M and out.shape[1] >= N
+        d.C, d.ldc = _ptr(out), ldc
+    d.CS, d.CS_pos = _ptr(out_s3), _ptr(out_s3_pos)
+    if out_s3_pos is not None:
+        pos, pr = pos                # the table in P8 order (pos8()), pos_rows its true row count
+        assert pos.numel() == (pr + 31) // 32 * 32 * N
+        d.pos, d.pos_rows = _ptr(pos), pr
+    d.res_s3, d.gamma, d.beta, d.eps = _ptr(res_s3), _ptr(gamma), _ptr(beta), eps
+    nbytes = 6.0 * (M * K + 2 * F * K) + (4.0 * M * N if out is not None else 0.0) + \
+        6.0 * M * N * ((out_s3 is not None) + (out_s3_pos is not None) + (res_s3 is not None))
+    _check(_launch("k_gemm_s3_ffn", 2.0 * M * F * (K + N), nbytes,
+                   lambda: lib().pn_gemm_s3_ffn_f32(C.byref(d), _stream()),
+                   meta=(M, N, F, 1, False)), "pn_gemm_s3_ffn_f32")
 
 
 def layernorm_rows(x, gamma, beta, out, eps=1e-5):
