@@ -1261,6 +1261,10 @@ int64_t pn_s3_bytes(int rows, int K);
  * ld % 4 == 0, 16-byte aligned).  Rows of the last block beyond `rows` are written as zeros. */
 int pn_s3_split_f32(const float* X, int64_t ld, const float* add, int add_rows, void* S, int rows,
                     int K, void* stream);
+/* Both at once from one read of X: S = split(X), S_add = split(X + add[r % add_rows]) (add
+ * required); bit for bit the two pn_s3_split_f32 calls. */
+int pn_s3_split2_f32(const float* X, int64_t ld, const float* add, int add_rows, void* S, void* S_add,
+                     int rows, int K, void* stream);
 /* The exact fp32 values back: X[r][0:K] = x0 + x1 + x2. */
 int pn_s3_join_f32(const void* S, float* X, int64_t ld, int rows, int K, void* stream);
 /*   out[m][n] = act( sum_k A*[m][k] W[n][k] + bias[n] ),   A* = A2 for n >= a2_from_col, else A
@@ -1312,6 +1316,27 @@ typedef struct pn_gemm_s3_ffn_desc {
   const void* res_s3;  const float* gamma;  const float* beta;  float eps;
 } pn_gemm_s3_ffn_desc;
 int pn_gemm_s3_ffn_f32(const pn_gemm_s3_ffn_desc* d, void* stream);
+/* pn_gemm_s3_f32's LayerNorm form with the activation operand as fp32 ROWS (k_gemm_s3_rows):
+ *   out[m][:] = LayerNorm(sum_k A[m][k] W[:][k] + bias + res[m][:]) * gamma + beta
+ * A fp32 [M][lda] (lda % 4 == 0, lda >= K, 16-byte aligned); W [N x K] and res_s3 [M x N] are S3
+ * operands; C / CS / CS_pos / pos as in pn_gemm_s3_desc.  The tile's waves split the rows into the
+ * three bf16 planes on their way into LDS, so the pn_s3_split_f32 pass in front of the GEMM and its
+ * S3 buffer are not needed.  Only rows 0 .. M-1 of A are read; the rows that pad the last row block
+ * enter as zeros, as pn_s3_split_f32 writes them.  Every output, padding rows of CS / CS_pos
+ * included, is bit for bit that of pn_s3_split_f32 -> pn_gemm_s3_f32 (gamma given).  Handled:
+ * N == 256, K % 32 == 0, gamma and beta given, act == 0; anything else returns PN_BAD_ARG without
+ * launching. */
+typedef struct pn_gemm_s3_rows_desc {
+  const float* A;  int64_t lda;
+  const void* W;   const float* bias;                   /* bias [N] or NULL */
+  int32_t M, N, K;
+  int32_t act;                                          /* 0 only */
+  float* C;        int64_t ldc;
+  void* CS;
+  void* CS_pos;    const float* pos;  int32_t pos_rows;
+  const void* res_s3;  const float* gamma;  const float* beta;  float eps;
+} pn_gemm_s3_rows_desc;
+int pn_gemm_s3_rows_ln_f32(const pn_gemm_s3_rows_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * The Mask2Former segmentation losses (csrc/seg_loss.hip; pair-net_amd/seg_losses.py drives them):

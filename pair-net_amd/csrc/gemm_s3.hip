@@ -37,6 +37,17 @@
 // A piece is waited for (vmcnt(0)) at the end of the issuing wave's NEXT phase (its MMA phase)
 // and read at least one barrier later; a ring slot is overwritten at least one barrier after its
 // last reader's phase.  Rings: A 3 stages x 18 KiB, W 2 stages x 48 KiB (150 KiB of LDS).
+//
+// fp32 rows as the A operand (k_gemm_s3_rows, the encoder's output_proj behind the sampling kernel).
+// The same tile, phases, rings and row epilogue; W still arrives by LDS-DMA, but A's 16-deep half
+// stages are FORMED by the tile: waves 0-2 of the issuing group load their row block's 8 floats per
+// lane in the READ phase in which k_gemm_s3 issues the DMA, hold them across the barrier, split them
+// (s3_split8, k_s3_split's lane mapping) behind the MFMAs of the following MMA phase and ds_write the
+// three planes to the lane-linear positions the DMA would have filled -- read() is the same.  Ring
+// rules for those register-written halves: written (lgkmcnt(0) at the phase's drain_bar) one barrier
+// before the first reader's READ phase, and at least two phases after the slot's last ds_read; the
+// phase table is at the kernel and in labnotes R35.1.  Rows at or beyond M are never loaded and
+// enter as zeros.  No split pass and no S3 copy of the sampled rows exist in memory.
 #include "common.h"
 #include "s3_common.h"
 
@@ -80,6 +91,39 @@ __global__ __launch_bounds__(256) void k_s3_split(const float* __restrict__ X, i
   s3_frag p0, p1, p2;
   s3_split8(v, p0, p1, p2);
   uint4* o = S + piece * 192 + lane;
+  o[0] = p0.u; o[64] = p1.u; o[128] = p2.u;
+}
+
+// The same pass with two outputs from ONE read of X: S = split(X) and SP = split(X + add) (the
+// encoder's entry: tokens and tokens + positions).  The additions and the splits are k_s3_split's.
+__global__ __launch_bounds__(256) void k_s3_split2(const float* __restrict__ X, int64_t ld,
+                                                   const float* __restrict__ add, int add_rows,
+                                                   uint4* __restrict__ S, uint4* __restrict__ SP, int R, int K) {
+  const int KB = K >> 4;
+  const int lane = threadIdx.x & 63;
+  const int64_t piece = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t npieces = (int64_t)((R + 31) >> 5) * KB;
+  if (piece >= npieces) return;
+  const int rb = (int)(piece / KB), kb = (int)(piece - (int64_t)rb * KB);
+  const int r = rb * 32 + (lane & 31), k = kb * 16 + (lane >> 5) * 8;
+  float v[8], w[8];
+  if (r < R) {
+    const float4 a = ld4(X + (int64_t)r * ld + k), b = ld4(X + (int64_t)r * ld + k + 4);
+    const float* p = add + (int64_t)(r % add_rows) * K + k;
+    const float4 c = ld4(p), d = ld4(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    w[0] = a.x + c.x; w[1] = a.y + c.y; w[2] = a.z + c.z; w[3] = a.w + c.w;
+    w[4] = b.x + d.x; w[5] = b.y + d.y; w[6] = b.z + d.z; w[7] = b.w + d.w;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = w[i] = 0.f;
+  }
+  s3_frag p0, p1, p2;
+  s3_split8(v, p0, p1, p2);
+  uint4* o = S + piece * 192 + lane;
+  o[0] = p0.u; o[64] = p1.u; o[128] = p2.u;
+  s3_split8(w, p0, p1, p2);
+  o = SP + piece * 192 + lane;
   o[0] = p0.u; o[64] = p1.u; o[128] = p2.u;
 }
 
@@ -881,6 +925,162 @@ __global__ __launch_bounds__(512, 1) void k_gemm_s3_ffn(const s3_args p, const u
   s3_ln_epilogue(acc2, p, smem, rb0, wave * 32, wave, lane);
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_gemm_s3<true> whose activation operand is fp32 ROWS (the sampling kernel's output in front of
+// output_proj): no split pass in memory between the two.  Geometry, W by LDS-DMA, read(), the
+// six-product order and the row epilogue are k_gemm_s3<true>'s; only the A path differs.  A 16-deep
+// half stage of A (3 row blocks x 3 planes, 9 KiB) is formed by waves 0-2 of the issuing group: wave
+// wq takes row block wq with k_s3_split's lane mapping (lane = (k half, row % 32)), two float4 loads
+// per lane, s3_split8, three ds_write_b128 at the lane-linear positions LDS-DMA filled in k_gemm_s3.
+//   G0 READ(s): loads A's first half of stage s+1   | G0 MMA(s): splits and writes it (slot (s+1) % 3)
+//   G1 READ(s): loads A's second half of stage s+2  | G1 MMA(s): splits and writes it (slot (s+2) % 3)
+// The 8 values per lane are held across the barrier between the two phases and written behind the
+// phase's MFMAs; every drain_bar waits vmcnt(0) and lgkmcnt(0), so a half is complete at the barrier
+// that ends its writer's MMA phase.  Ring rules (phases: G0 READ(s) = 2s+1, G0 MMA(s) = G1 READ(s) =
+// 2s+2, G1 MMA(s) = 2s+3): stage s+1's first half is written in phase 2s+2, first read in 2s+3, the
+// slot's last reader (G1 READ(s-2)) was phase 2s-2; stage s+2's second half is written in phase 2s+3,
+// first read in 2s+5, the slot's last reader (G1 READ(s-1)) was phase 2s.  Rows at or beyond M are
+// never loaded and enter the product as zeros (what k_s3_split writes into the padding rows), so the
+// outputs, padding rows of CS / CS_pos included, are bit for bit the split + k_gemm_s3<true> pair's.
+__global__ __launch_bounds__(512, 1) void k_gemm_s3_rows(const s3_args p, const float* __restrict__ Af,
+                                                         const int64_t lda) {
+  constexpr int MB = 3;
+  constexpr int AH = 9 * 64, AST = 2 * AH;           // uint4 per A half (16-deep) / A stage
+  constexpr int BH = 24 * 64, BST = 2 * BH;          // uint4 per W half / W stage
+  constexpr int BRING = 3 * AST;
+  __shared__ __attribute__((aligned(1024))) uint4 smem[3 * AST + 2 * BST];   // 150 KiB
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = wave >> 2, wq = wave & 3;
+  const int M = p.M, KB = p.K >> 4, S = KB >> 1;
+  const int RB = (M + 31) >> 5, mt = (RB + MB - 1) / MB;
+  const int rb0 = xcd_tile_index(blockIdx.x, mt) * MB;
+
+  // LDS-DMA pieces of this wave: per stage the six of W that are its own column block's (3 planes x
+  // 2 halves), as in k_gemm_s3_ffn: one wave-uniform base, constant piece offsets, the lane last
+  const int cb = grp * 4 + wq;
+  const uint4* gW = p.W + (int64_t)cb * KB * 192;
+  const int lW = cb * 3 * 64;
+  const unsigned ul = lane;
+  auto issueB = [&](int s) {
+    const uint4* g = gW + (int64_t)s * 384;
+    const int base = BRING + (s & 1) * BST + lW;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) s3_glds16(g + (h * 192 + q * 64) + ul, &smem[base + h * BH + q * 64]);
+  };
+  // A: waves 0-2 of a group own row block wq of the half stages their group forms
+  const bool aw = wq < 3;
+  const int arow = (rb0 + wq) * 32 + (lane & 31);
+  const bool aok = aw && arow < M;                   // rows at or beyond M are never read
+  const float* ga = Af + (int64_t)(aok ? arow : 0) * lda + (lane >> 5) * 8;
+  auto loadA = [&](int s, int half, float4& x, float4& y) {
+    x = y = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (aok) {
+      const float* g = ga + (2 * s + half) * 16;
+      x = ld4(g); y = ld4(g + 4);
+    }
+  };
+  auto writeA = [&](int as, int half, const float4& x, const float4& y) {   // where issueA put the half
+    if (!aw) return;
+    const float v[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+    s3_frag q0, q1, q2;
+    s3_split8(v, q0, q1, q2);
+    uint4* d = smem + as * AST + half * AH + wq * 3 * 64 + lane;
+    d[0] = q0.u; d[64] = q1.u; d[128] = q2.u;
+  };
+  s3_frag a[2][MB][3], b[2][3];
+  f32x16 acc[MB];
+#pragma unroll
+  for (int m = 0; m < MB; ++m)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
+  const int bfrag = cb * 3 * 64 + lane;
+  auto read = [&](int s, int as) {
+    const uint4* pa = smem + as * AST + lane;
+    const uint4* pb = smem + BRING + (s & 1) * BST + bfrag;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) a[h][m][q].u = pa[h * AH + (m * 3 + q) * 64];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) b[h][q].u = pb[h * BH + q * 64];
+    }
+  };
+  auto mma = [&] {                                   // k_gemm_s3's order
+    constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int q = 0; q < 6; ++q)
+#pragma unroll
+        for (int m = 0; m < MB; ++m)
+          acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[h][PB[q]].v, a[h][m][PA[q]].v, acc[m], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);               // (the split and its ds_writes stand behind the MFMAs)
+  };
+  auto bar = [&] {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto drain_bar = [&] {                             // vmcnt(0) (LDS-DMA) and lgkmcnt(0) (ds_write)
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0x0070);
+    bar();
+  };
+  // ---- prologue: stage 0 whole (every wave its W pieces, A's halves one per group), and A's
+  // second half of stage 1 ----
+  issueB(0);
+  {
+    float4 x0, y0, x1, y1;
+    loadA(0, grp, x0, y0);
+    if (grp == 1 && S > 1) loadA(1, 1, x1, y1);
+    writeA(0, grp, x0, y0);
+    if (grp == 1 && S > 1) writeA(1, 1, x1, y1);
+  }
+  drain_bar();
+  if (grp == 0) {
+    int as = 0;
+    for (int s = 0; s < S; ++s) {
+      const int as1 = as == 2 ? 0 : as + 1;
+      const bool more = s + 1 < S;
+      float4 hx, hy;
+      __builtin_amdgcn_s_setprio(1);
+      read(s, as);
+      if (more) { loadA(s + 1, 0, hx, hy); issueB(s + 1); }
+      __builtin_amdgcn_s_setprio(0);
+      bar();
+      mma();
+      if (more) writeA(as1, 0, hx, hy);
+      drain_bar();
+      as = as1;
+    }
+  } else {
+    bar();
+    int as = 0;
+    for (int s = 0; s < S; ++s) {
+      const int as2 = as == 0 ? 2 : as - 1;          // (s + 2) % 3
+      const bool more2 = s + 2 < S;
+      float4 hx, hy;
+      __builtin_amdgcn_s_setprio(1);
+      read(s, as);
+      if (more2) loadA(s + 2, 1, hx, hy);
+      if (s + 1 < S) issueB(s + 1);
+      __builtin_amdgcn_s_setprio(0);
+      bar();
+      mma();
+      if (more2) writeA(as2, 1, hx, hy);
+      if (s + 1 < S) drain_bar();
+      as = as == 2 ? 0 : as + 1;
+    }
+  }
+  s3_ln_epilogue(acc, p, smem, rb0, wave * 32, wave, lane);
+}
+
 // Leftover columns (N % 256 of at most 64, e.g. the last 32 of the encoder's 544-column
 // [value | offsets | logits] projection): one wave per (row block, column block), operands straight
 // to registers -- nothing is shared, 0.4 GFLOP, latency-bound and short.
@@ -933,6 +1133,16 @@ extern "C" int pn_s3_split_f32(const float* X, int64_t ld, const float* add, int
   return PN_LAUNCH_CHECK();
 }
 
+extern "C" int pn_s3_split2_f32(const float* X, int64_t ld, const float* add, int add_rows, void* S,
+                                void* S_add, int rows, int K, void* stream) {
+  if (!X || !S || !S_add || !add || add_rows <= 0 || rows <= 0 || K <= 0 || K % 16 || ld % 4)
+    return PN_BAD_ARG;
+  const int64_t np = (int64_t)((rows + 31) / 32) * (K / 16);
+  k_s3_split2<<<dim3((unsigned)((np + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
+      X, ld, add, add_rows, (uint4*)S, (uint4*)S_add, rows, K);
+  return PN_LAUNCH_CHECK();
+}
+
 extern "C" int pn_s3_join_f32(const void* S, float* X, int64_t ld, int rows, int K, void* stream) {
   if (!X || !S || rows <= 0 || K <= 0 || K % 16 || ld % 4) return PN_BAD_ARG;
   const int64_t np = (int64_t)((rows + 31) / 32) * (K / 16);
@@ -959,6 +1169,28 @@ extern "C" int pn_gemm_s3_ffn_f32(const pn_gemm_s3_ffn_desc* d, void* stream) {
   a.res = nullptr; a.ldres = 0;
   const int RB = (d->M + 31) / 32, mt = (RB + 2) / 3;
   k_gemm_s3_ffn<<<dim3(mt), dim3(512), 0, (hipStream_t)stream>>>(a, (const uint4*)d->W1, d->b1);
+  return PN_LAUNCH_CHECK();
+}
+
+extern "C" int pn_gemm_s3_rows_ln_f32(const pn_gemm_s3_rows_desc* d, void* stream) {
+  if (!d || !d->A || !d->W || d->M <= 0) return PN_BAD_ARG;
+  if (d->N != 256 || d->K <= 0 || d->K % 32) return PN_BAD_ARG;
+  if (d->lda % 4 || d->lda < d->K || ((uintptr_t)d->A & 15)) return PN_BAD_ARG;
+  if (d->act) return PN_BAD_ARG;                            // no activation in front of the LayerNorm
+  if (!d->gamma || !d->beta) return PN_BAD_ARG;             // the row epilogue is the LayerNorm one
+  if (!d->C && !d->CS && !d->CS_pos) return PN_BAD_ARG;
+  if (d->C && (d->ldc % 4 || d->ldc < d->N)) return PN_BAD_ARG;
+  if (d->CS_pos && (!d->pos || d->pos_rows <= 0)) return PN_BAD_ARG;
+  s3_args a;
+  a.A = nullptr; a.A2 = nullptr; a.a2_from_tile = 0;
+  a.W = (const uint4*)d->W; a.bias = d->bias;
+  a.C = d->C; a.ldc = d->ldc; a.CS = (uint4*)d->CS; a.CSP = (uint4*)d->CS_pos;
+  a.RES = (const uint4*)d->res_s3; a.gamma = d->gamma; a.beta = d->beta; a.pos = d->pos;
+  a.pos_rows = d->pos_rows; a.eps = d->eps;
+  a.M = d->M; a.N = d->N; a.K = d->K; a.relu = 0; a.nout = d->N;
+  a.res = nullptr; a.ldres = 0;
+  const int RB = (d->M + 31) / 32, mt = (RB + 2) / 3;
+  k_gemm_s3_rows<<<dim3(mt), dim3(512), 0, (hipStream_t)stream>>>(a, d->A, d->lda);
   return PN_LAUNCH_CHECK();
 }
 

@@ -182,6 +182,11 @@ class CrossHead2:
         # registers through LDS into FFN-2's MFMAs instead of through pl.HS, 270 MB of traffic per
         # layer at 800 x 1333; bit-identical, 0 restores the two launches (labnotes R34)
         self.fuse_encoder_ffn = 1
+        # the encoder layers' output_proj + identity + norms.0 reads the sampling kernel's fp32 rows
+        # itself (pn_gemm_s3_rows_ln_f32: its waves split the rows on their way into LDS) instead of
+        # a split pass pl.S -> pl.SS in front of it, one launch and 56 MB of traffic per layer at
+        # 800 x 1333; bit-identical, 0 restores the split pass (labnotes R35)
+        self.enc_proj_reads_rows = 1
         # lateral GroupNorm and the top-down upsample-add as one pass over the stride-4 map
         # (pn_groupnorm_upadd_nhwc_f32) instead of two, bit-identical.  Off by default: 78 against
         # 90 us stand-alone, but no difference in the pipelined step beyond its run-to-run spread
@@ -829,7 +834,11 @@ class CrossHead2:
         the producing kernel's epilogue: XS = tokens, XPS = tokens + positions (the reference's
         `query + query_pos`), X1S = norms.0 output, HS = FFN hidden rows; residuals are read back
         from those planes (exact).  fp32 rows exist where a non-GEMM consumer reads them: VOA (the
-        sampling kernel) and the final memory pl.X."""
+        sampling kernel) and the final memory pl.X -- and S, the sampling kernel's output, which
+        output_proj reads as rows (`enc_proj_reads_rows`).  Live per layer with the default
+        switches: XS, XPS, VOA, S, X1S; SS (the split of S) is written only with
+        `enc_proj_reads_rows` off or `msda_s3_out` on, HS only with `fuse_encoder_ffn` off: both
+        stay carved either way."""
         w, B, SN = self.w, pl.B, pl.SN
         pd = "pixel_decoder."
         M, F = B * SN, self.enc_ffn
@@ -837,8 +846,8 @@ class CrossHead2:
         pos8 = (pl.enc_pos8, SN)
         # the one-launch FFN handles a hidden width that is a multiple of 256 (the config's 1024)
         fuse_ffn = bool(getattr(self, "fuse_encoder_ffn", 0)) and F % 256 == 0
-        hip.s3_split(X2, pl.XS)
-        hip.s3_split(X2, pl.XPS, add=pl.enc_pos)
+        rows_proj = bool(getattr(self, "enc_proj_reads_rows", 0)) and not self.msda_s3_out
+        hip.s3_split(X2, pl.XS, add=pl.enc_pos, out_add=pl.XPS)      # one read of the tokens
         for i in range(self.num_enc_layers):
             p = pd + "encoder.layers.%d." % i
             a = p + "attentions.0."
@@ -849,10 +858,15 @@ class CrossHead2:
                 hip.msda(pl.VOA, 544, pl.VOA.view(-1)[256:], 544, pl.SS, B, pl.shapes, s3_out=True)
             else:
                 hip.msda(pl.VOA, 544, pl.VOA.view(-1)[256:], 544, pl.S, B, pl.shapes)
-                hip.s3_split(pl.S.view(-1, 256), pl.SS)
-            hip.gemm_s3(pl.SS, w[a + "output_proj.weight.s3"], M, 256, 256,
-                        bias=w[a + "output_proj.bias"], out_s3=pl.X1S, res_s3=pl.XS,
+                if not rows_proj:
+                    hip.s3_split(pl.S.view(-1, 256), pl.SS)
+            proj = dict(bias=w[a + "output_proj.bias"], out_s3=pl.X1S, res_s3=pl.XS,
                         gamma=w[p + "norms.0.weight"], beta=w[p + "norms.0.bias"])
+            if rows_proj:                # (pl.SS stays carved and is not written)
+                hip.gemm_s3_rows_ln(pl.S.view(-1, 256), w[a + "output_proj.weight.s3"], M, 256, 256,
+                                    **proj)
+            else:
+                hip.gemm_s3(pl.SS, w[a + "output_proj.weight.s3"], M, 256, 256, **proj)
             tail = dict(res_s3=pl.X1S, gamma=w[p + "norms.1.weight"], beta=w[p + "norms.1.bias"],
                         out=X2 if last else None, out_s3=None if last else pl.XS,
                         out_s3_pos=None if last else pl.XPS, pos=pos8)
@@ -1171,6 +1185,7 @@ class CrossHead2:
                tuple(self.enc_fused_ln), self.group_input_convs,
                getattr(self, "fuse_mask_pack", True), self.gemm_arithmetic, self.msda_s3_out,
                self._fused_pair_masks(), bool(getattr(self, "fuse_encoder_ffn", 0)),
+               bool(getattr(self, "enc_proj_reads_rows", 0)),
                getattr(self, "gather_mask_stencil", True), getattr(self, "fuse_lateral_upadd", False))
         if pl.graph_cfg != cfg:          # a captured graph bakes these switches in
             pl.graph_a = pl.graph_b = None

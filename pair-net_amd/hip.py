@@ -60,6 +60,16 @@ class GemmS3FfnDesc(C.Structure):
                 ("res_s3", _vp), ("gamma", _vp), ("beta", _vp), ("eps", _f32)]
 
 
+class GemmS3RowsDesc(C.Structure):
+    _fields_ = [("A", _vp), ("lda", _i64),
+                ("W", _vp), ("bias", _vp),
+                ("M", _i32), ("N", _i32), ("K", _i32), ("act", _i32),
+                ("C", _vp), ("ldc", _i64),
+                ("CS", _vp),
+                ("CS_pos", _vp), ("pos", _vp), ("pos_rows", _i32),
+                ("res_s3", _vp), ("gamma", _vp), ("beta", _vp), ("eps", _f32)]
+
+
 _SIGS = {
     "pn_abi_version": (C.c_int, []),
     "pn_s3_bytes": (_i64, [_i32, _i32]),
@@ -67,6 +77,8 @@ _SIGS = {
     "pn_s3_join_f32": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),
     "pn_gemm_s3_f32": (C.c_int, [C.POINTER(GemmS3Desc), _vp]),
     "pn_gemm_s3_ffn_f32": (C.c_int, [C.POINTER(GemmS3FfnDesc), _vp]),
+    "pn_gemm_s3_rows_ln_f32": (C.c_int, [C.POINTER(GemmS3RowsDesc), _vp]),
+    "pn_s3_split2_f32": (C.c_int, [_vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _vp]),
     "pn_gemm_f32": (C.c_int, [C.POINTER(GemmDesc), _vp]),
     "pn_gemm_variant": (C.c_int, [C.POINTER(GemmDesc)]),
     "pn_gemm_grid_size": (C.c_int, [C.POINTER(GemmDesc)]),
@@ -697,9 +709,11 @@ def pos8(pos):
     return p.view(rb, 32, cols // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
 
 
-def s3_split(x, out, add=None):
+def s3_split(x, out, add=None, out_add=None):
     """out (an S3 buffer, any dtype, >= s3_floats(rows, K) * 4 bytes) = split(x + add[row % len(add)])
-    for 2-D fp32 rows x: the three-bf16-plane operand format of gemm_s3 (include/pairnet_hip.h)."""
+    for 2-D fp32 rows x: the three-bf16-plane operand format of gemm_s3 (include/pairnet_hip.h).
+    With `out_add`: out = split(x) and out_add = split(x + add) from one read of x (one launch,
+    bit for bit the two separate calls)."""
     rows, ld = _rowmajor(x)
     K = x.shape[1]
     assert out.numel() * out.element_size() >= s3_floats(rows, K) * 4
@@ -707,6 +721,14 @@ def s3_split(x, out, add=None):
     if add is not None:
         ar, lda = _rowmajor(add)
         assert lda == K and add.shape[1] == K
+    if out_add is not None:
+        assert add is not None
+        assert out_add.numel() * out_add.element_size() >= s3_floats(rows, K) * 4
+        _check(_launch("k_s3_split2", 0.0, 16.0 * rows * K,
+                       lambda: lib().pn_s3_split2_f32(_ptr(x), ld, _ptr(add), ar, _ptr(out),
+                                                      _ptr(out_add), rows, K, _stream())),
+               "pn_s3_split2_f32")
+        return
     _check(_launch("k_s3_split", 0.0, 10.0 * rows * K,
                    lambda: lib().pn_s3_split_f32(_ptr(x), ld, _ptr(add), ar, _ptr(out), rows, K,
                                                  _stream())), "pn_s3_split_f32")
@@ -780,6 +802,36 @@ def gemm_s3_ffn(x, w1, w2, M, N, K, F, *, b1=None, b2=None, res_s3=None, gamma=N
     _check(_launch("k_gemm_s3_ffn", 2.0 * M * F * (K + N), nbytes,
                    lambda: lib().pn_gemm_s3_ffn_f32(C.byref(d), _stream()),
                    meta=(M, N, F, 1, False)), "pn_gemm_s3_ffn_f32")
+
+
+def gemm_s3_rows_ln(a, w, M, N, K, *, bias=None, res_s3=None, gamma=None, beta=None, eps=1e-5,
+                    out=None, out_s3=None, out_s3_pos=None, pos=None):
+    """gemm_s3's LayerNorm form reading its activation operand as fp32 rows (csrc/gemm_s3.hip,
+    k_gemm_s3_rows): LayerNorm(a @ w.T + bias + res) * gamma + beta, bit for bit the
+    s3_split(a) -> gemm_s3(res_s3=, gamma=, beta=) pair without the split pass and its buffer.
+    a is 2-D fp32 rows [M x K] (row pitch % 4 == 0); w, res_s3, out_s3, out_s3_pos are S3 buffers;
+    out is 2-D fp32 rows.  N == 256, K % 32 == 0 and a LayerNorm only: the library refuses the rest."""
+    d = GemmS3RowsDesc()
+    Ma, lda = _rowmajor(a)
+    assert Ma >= M
+    d.A, d.lda = _ptr(a), lda
+    d.W, d.bias = _ptr(w), _ptr(bias)
+    d.M, d.N, d.K, d.act = M, N, K, 0
+    if out is not None:
+        Mo, ldc = _rowmajor(out)
+        assert Mo == M and out.shape[1] >= N
+        d.C, d.ldc = _ptr(out), ldc
+    d.CS, d.CS_pos = _ptr(out_s3), _ptr(out_s3_pos)
+    if out_s3_pos is not None:
+        pos, pr = pos                # the table in P8 order (pos8()), pos_rows its true row count
+        assert pos.numel() == (pr + 31) // 32 * 32 * N
+        d.pos, d.pos_rows = _ptr(pos), pr
+    d.res_s3, d.gamma, d.beta, d.eps = _ptr(res_s3), _ptr(gamma), _ptr(beta), eps
+    nbytes = 4.0 * M * K + 6.0 * N * K + (4.0 * M * N if out is not None else 0.0) + \
+        6.0 * M * N * ((out_s3 is not None) + (out_s3_pos is not None) + (res_s3 is not None))
+    _check(_launch("k_gemm_s3_rows", 2.0 * M * N * K, nbytes,
+                   lambda: lib().pn_gemm_s3_rows_ln_f32(C.byref(d), _stream()),
+                   meta=(M, N, K, 1, False)), "pn_gemm_s3_rows_ln_f32")
 
 
 def layernorm_rows(x, gamma, beta, out, eps=1e-5):
