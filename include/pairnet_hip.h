@@ -1670,6 +1670,82 @@ int pn_train_log_row_f32(const float* const* scalars, int T, uint32_t loss_mask,
 int pn_train_log_window_f32(const float* ring, int rows, int ld, int n, int T, float* record,
                             void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * The plain Deformable-DETR detector (configs/deformable_detr/od_r101_vg.py:3-96, `DeformableDETR`
+ * with a `DeformableDETRHead`): its loss ([3P] mmdet `DETRHead.loss_single`; the in-tree statement
+ * is the commented text at pairnet_bbox_head.py:596-642) and its box results.  csrc/det_loss.hip;
+ * composed in det_losses.py / det_head.py.  Entries added at ABI 34 (adding entries is compatible).
+ * ------------------------------------------------------------------------- */
+/* pn_box_match_cost_f32's cost, cell for cell and in the same operation order, for P problems of
+ * their own row counts in ONE launch: the HungarianAssigner of od_r101_vg.py:87-94 (FocalLossCost
+ * 2.0, BBoxL1Cost 5.0 xywh, IoUCost giou 2.0) for every decoder layer and for the per-token
+ * proposals (pairnet_bbox_head.py:596-642 states the per-layer term).
+ *   cls [rows_len][nc] / box [rows_len][4]   the problems' rows, concatenated
+ *   tab [P][6] int64 = {offset of the rows x G block in cost, rows (1 .. 65536), G (1 .. 1024),
+ *                       offset of the labels in gt_labels, offset of the boxes in gt_bboxes (in
+ *                       boxes), offset of the first row in cls / box}
+ *   factor [P][4] = (img_w, img_h, img_w, img_h) of the problem's image
+ * A label array of zeros gives the proposal term's binarised labels.  max_cells: the largest
+ * rows * G of the table (sizes the grid).  The table lives on the device, so this is the CALLER's
+ * contract: cells of a block past max_cells are not written, and the entry cannot tell.  A table row outside a buffer or a range leaves its block
+ * untouched; a label outside [0, nc) gives a NaN cell.  One cell per lane, no atomics, bitwise
+ * reproducible.  PN_BAD_ARG before the launch: a NULL, a non-positive length, max_cells above
+ * 65536 * 1024, P outside [1, 65535], nc outside [1, 256]. */
+int pn_det_match_cost_f32(const float* cls, const float* box, int64_t rows_len,
+                          const int64_t* gt_labels, int64_t labels_len, const float* gt_bboxes,
+                          int64_t boxes_len, const float* factor, const int64_t* tab, float* cost,
+                          int64_t cost_len, int64_t max_cells, int P, int nc, float w_cls,
+                          float w_reg, float w_iou, float alpha, float gamma, float eps,
+                          float iou_eps, void* stream);
+/* `loss_cls` of every term in one streaming launch (od_r101_vg.py:80-82: FocalLoss, sigmoid,
+ * gamma 2, alpha 0.25, weight 2.0; pairnet_bbox_head.py:596-642: summed over rows * C, divided by
+ * the term's avg_factor).  x / grad [rows][C] contiguous and 16-byte aligned; labels [rows] int32
+ * (C = background), term [rows] int32 in [0, T), avg [T] (the factors, > 0).
+ *   element   mmdet `py_sigmoid_focal_loss`: BCE-with-logits (stable form) * alpha_t * pt^gamma
+ *   grad      (w_cls / avg[term]) * d element / d x, every element written (0 for a row whose
+ *             term is outside [0, T))
+ *   out[t]    w_cls * (sum of term t's elements / avg[t])
+ * The sums go through partial [pn_det_focal_partials(rows, C, T)] floats (per workgroup and term)
+ * and a second fixed-order pass: no float atomics, bitwise reproducible.  The block is read and
+ * written 16 bytes at a time whatever C is (an element's row is its flat index / C); the last
+ * (rows * C) % 4 elements go one by one.  A label outside [0, C] makes its row's loss and gradient
+ * NaN.  PN_BAD_ARG before the launch: a NULL, rows <= 0, C outside [1, 256], T outside [1, 16],
+ * rows * C >= 2^31, a short `partial`, x or grad not 16-byte aligned (pn_det_focal_partials
+ * returns 0 for such shapes). */
+int64_t pn_det_focal_partials(int64_t rows, int C, int T);
+int pn_det_focal_f32(const float* x, const int32_t* labels, const int32_t* term, const float* avg,
+                     float* grad, float* partial, int64_t partial_len, float* out, int64_t rows,
+                     int C, int T, float w_cls, float alpha, float gamma, void* stream);
+/* `loss_bbox` (L1Loss 5.0, od_r101_vg.py:83) and `loss_iou` (GIoULoss 2.0, :84) of every term over
+ * the M matched pairs (pairnet_bbox_head.py:596-642): pairs [M][4] int32 = {row of the prediction
+ * in box / grad, ground-truth box, row of factor, term}, grouped by term with term t owning
+ * [term_off[t], term_off[t + 1]).  Targets are cxcywh(gt / factor); GIoU compares cxcywh_to_xyxy(.)
+ * * factor of both sides with mmdet's bbox_overlaps(is_aligned, eps = iou_eps) clamps.
+ *   out[t][0] = w_bbox * (sum |pred - target| / avg[t]),  out[t][1] = w_iou * (sum (1 - GIoU) / avg[t])
+ * One workgroup per term, fixed order, bitwise reproducible.  grad [rows_len][4] must come zeroed:
+ * the matched rows receive d(out[t][0] + out[t][1]) / d cxcywh (|d| has derivative 0 at 0; min /
+ * max / clamp as autograd, any subgradient at exact ties).  A pair that points outside a buffer
+ * makes its term NaN and writes no gradient.  M == 0 is legal.  PN_BAD_ARG before the launch: a
+ * NULL (pairs / gt_bboxes may be NULL at M == 0), T outside [1, 16], a non-positive or >= 2^31
+ * length, M < 0. */
+int pn_det_box_loss_f32(const float* box, int64_t rows_len, const float* gt_bboxes,
+                        int64_t boxes_len, const float* factor, int64_t factor_len,
+                        const int32_t* pairs, const int32_t* term_off, int64_t M, int T,
+                        const float* avg, float* grad, float* out, float w_bbox, float w_iou,
+                        float iou_eps, void* stream);
+/* Box results behind the ranking ([3P] mmdet `DETRHead._get_bboxes_single` for a sigmoid classifier,
+ * test_cfg max_per_img of od_r101_vg.py:95; the head whose loss pairnet_bbox_head.py:596-642
+ * states): idx [B][K] flat indices into the image's Q * C logits, best first (pn_topk_strided_f32).
+ *   labels[b][k] = idx % C;  det[b][k] = (clamp(cxcywh_to_xyxy(box[b][idx / C]) * (w, h, w, h), 0,
+ *   (w, h, w, h)) [/ scale_factor if rescale], sigmoid(cls[b][idx]))
+ * meta [B][6] = {img_h, img_w, scale_factor[0..3]}.  mmdet's operation order, no fused multiply-adds;
+ * every element of det [B][K][5] and labels [B][K] (int64) is written (an index outside [0, Q * C):
+ * NaN row, label -1).  PN_BAD_ARG: a NULL, a non-positive size, C > 256, Q * C > 65536, K > Q * C,
+ * B * K >= 2^24, B * Q * C >= 2^31. */
+int pn_det_results_f32(const float* cls, const float* box, const int64_t* idx, const float* meta,
+                       float* det, int64_t* labels, int B, int Q, int C, int K, int rescale,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,8 @@
 """Public names of the package (what a user of the reference looks for)."""
 from .config import (ConfigDict, baseline_head_cfg, baseline_r50, bbox_head_cfg,  # noqa: F401
-                     channel_mapper_cfg, cross_r101_vg, load_config, pairnet_rnext101_vg,
+                     channel_mapper_cfg, cross_r101_vg, det_head_cfg, det_test_pipeline_cfg, det_train_cfg,
+                     load_config,
+                     od_r101_vg, od_rnext101_vg, pairnet_rnext101_vg,
                      pairnet_head_cfg, pairnet_r50, pairnet_swin, psgtr2_head_cfg, psgtr2_r50,
                      psgtr2_train_cfg,
                      swin_backbone_cfg, test_pipeline_cfg, train_pipeline_cfg)
@@ -21,6 +23,9 @@ from .baseline_train import BaselineTrainer  # noqa: F401
 from .bbox_train import BBoxTrainer  # noqa: F401
 from .psgtr2_train import PSGTr2Trainer  # noqa: F401
 from .bbox_losses import CrossHeadBBoxLoss  # noqa: F401
+from .det_head import DeformableDETRHead  # noqa: F401
+from .det_losses import DeformableDETRLoss  # noqa: F401
+from .det_detector import DeformableDETR  # noqa: F401
 from .seg_losses import Mask2FormerLoss  # noqa: F401
 from .baseline_losses import BaselineRelationLoss  # noqa: F401
 from .psgtr2_losses import PSGTrHead2Loss  # noqa: F401
@@ -45,4 +50,6 @@ __all__ = ["ConfigDict", "load_config", "pairnet_head_cfg", "pairnet_r50", "Cros
            "BaselineRelationLoss", "BBoxTailGrad", "BBoxTrainer", "CrossHeadBBoxLoss",
            "PSGTrHead2Loss", "psgtr2_train_cfg", "PSGTr2HeadGrad", "PSGTr2Trainer",
            "ResNeXtHip", "pairnet_rnext101_vg",
+           "DeformableDETR", "DeformableDETRHead", "DeformableDETRLoss", "od_r101_vg",
+           "od_rnext101_vg", "det_head_cfg", "det_train_cfg", "det_test_pipeline_cfg",
            "EpochRunner", "TrainLog", "epoch_order", "resume", "save_checkpoint"]

@@ -66,7 +66,6 @@ class CrossHeadBBox(CrossHead2):
         relation_decoder = ConfigDict(relation_decoder)
         if not (as_two_stage and with_box_refine and transformer.get("as_two_stage", False)):
             raise NotImplementedError("two-stage, box-refining trunk only (see module docstring)")
-        enc, dec = transformer.encoder, transformer.decoder
         got = tuple(relation_decoder.transformerlayers.get("operation_order", ()))
         if got != self.RELATION_ORDER or relation_decoder.transformerlayers.get("norm_cfg"):
             raise NotImplementedError("relation decoder: post-norm LayerNorm layers in the order "
@@ -74,16 +73,7 @@ class CrossHeadBBox(CrossHead2):
         act = relation_decoder.transformerlayers.ffn_cfgs.get("act_cfg", dict(type="ReLU"))
         if act.get("type") != "ReLU":
             raise NotImplementedError("relation decoder FFN activation %s" % act.get("type"))
-        if tuple(enc.transformerlayers.operation_order) != ("self_attn", "norm", "ffn", "norm") or \
-                tuple(dec.transformerlayers.operation_order) != (
-                    "self_attn", "norm", "cross_attn", "norm", "ffn", "norm"):
-            raise NotImplementedError("Deformable-DETR operation orders only")
-        if embed_dims != 256 or num_reg_fcs != 2 or positional_encoding["num_feats"] != 128 \
-                or not positional_encoding.get("normalize", False):
-            raise NotImplementedError("256 channels, 2 hidden box-branch layers, normalised "
-                                      "128-feature sine encoding")
-        self.pe_offset = float(positional_encoding.get("offset", 0.0))
-        self.pe_temperature = float(positional_encoding.get("temperature", 10000))
+        self._read_trunk_cfg(transformer, positional_encoding, embed_dims, num_reg_fcs)
         loss_cls = loss_cls or {}
         self.cls_out_channels = num_classes if loss_cls.get("use_sigmoid", False) \
             else num_classes + 1
@@ -93,12 +83,6 @@ class CrossHeadBBox(CrossHead2):
         self.num_obj_query = self.KEPT                     # the PPN's query count
         self.num_rel_query = num_rel_query
         self.use_mask = use_mask
-        self.embed_dims, self.n_heads, self.num_heads = embed_dims, 8, 8
-        self.as_two_stage, self.with_box_refine = True, True
-        self.num_levels = transformer.get("num_feature_levels", 4)
-        self.num_enc_layers, self.num_dec_layers = enc.num_layers, dec.num_layers
-        self.enc_ffn = enc.transformerlayers.get("feedforward_channels", 1024)
-        self.dec_ffn = dec.transformerlayers.get("feedforward_channels", 1024)
         self.num_rel_layers = relation_decoder.num_layers
         self.rel_ffn = relation_decoder.transformerlayers.ffn_cfgs.feedforward_channels
         self.test_cfg, self.train_cfg = test_cfg, train_cfg
@@ -110,6 +94,31 @@ class CrossHeadBBox(CrossHead2):
         if self.num_levels != 4 or self.num_proposals > 512 or self.num_proposals < self.KEPT \
                 or self.cls_out_channels > 256 or num_rel_query > 128:
             raise NotImplementedError("4 levels, <= 512 proposals, <= 256 classes")
+        self._init_trunk_state()
+
+    def _read_trunk_cfg(self, transformer, positional_encoding, embed_dims, num_reg_fcs):
+        """What both heads on this trunk (this class, det_head.py) read from the trunk's config."""
+        enc, dec = transformer.encoder, transformer.decoder
+        if tuple(enc.transformerlayers.operation_order) != ("self_attn", "norm", "ffn", "norm") or \
+                tuple(dec.transformerlayers.operation_order) != (
+                    "self_attn", "norm", "cross_attn", "norm", "ffn", "norm"):
+            raise NotImplementedError("Deformable-DETR operation orders only")
+        if embed_dims != 256 or num_reg_fcs != 2 or positional_encoding["num_feats"] != 128 \
+                or not positional_encoding.get("normalize", False):
+            raise NotImplementedError("256 channels, 2 hidden box-branch layers, normalised "
+                                      "128-feature sine encoding")
+        self.pe_offset = float(positional_encoding.get("offset", 0.0))
+        self.pe_temperature = float(positional_encoding.get("temperature", 10000))
+        self.embed_dims, self.n_heads, self.num_heads = embed_dims, 8, 8
+        self.as_two_stage, self.with_box_refine = True, True
+        self.num_levels = transformer.get("num_feature_levels", 4)
+        self.num_enc_layers, self.num_dec_layers = enc.num_layers, dec.num_layers
+        self.enc_ffn = enc.transformerlayers.get("feedforward_channels", 1024)
+        self.dec_ffn = dec.transformerlayers.get("feedforward_channels", 1024)
+
+    def _init_trunk_state(self):
+        """Parameters, plan / arena tables and scheduling switches: the state every head on this
+        trunk starts from (called last by both constructors)."""
         self._params = OrderedDict((k, torch.zeros(s)) for k, s in self.param_shapes().items())
         self.device, self.w = None, None
         self._plans, self._post, self._consts = PlanCache(), OrderedDict(), {}
@@ -135,6 +144,18 @@ class CrossHeadBBox(CrossHead2):
         for i, (ci, co) in enumerate(((1, 64), (64, 64), (64, 1))):
             s["update_importance.conv_layers.%d.0.weight" % i] = (co, ci, 7, 7)
             s["update_importance.conv_layers.%d.0.bias" % i] = (co,)
+        self._trunk_param_shapes(s)
+        for mlp in ("sub_query_update", "obj_query_update"):
+            for j in (0, 2, 4):
+                s["%s.%d.weight" % (mlp, j)] = (256, 256)
+                s["%s.%d.bias" % (mlp, j)] = (256,)
+        s["rel_cls_embed.weight"] = (self.num_relations, 256)
+        s["rel_cls_embed.bias"] = (self.num_relations,)
+        self._branch_param_shapes(s)
+        return s
+
+    def _trunk_param_shapes(self, s):
+        """mmdet DeformableDetrTransformer's names (shared with det_head.py)."""
         t = "transformer."
         s[t + "level_embeds"] = (4, 256)
 
@@ -170,12 +191,10 @@ class CrossHeadBBox(CrossHead2):
             s[t + name + ".bias"] = (n,)
             s[t + name + "_norm.weight"] = (n,)
             s[t + name + "_norm.bias"] = (n,)
-        for mlp in ("sub_query_update", "obj_query_update"):
-            for j in (0, 2, 4):
-                s["%s.%d.weight" % (mlp, j)] = (256, 256)
-                s["%s.%d.bias" % (mlp, j)] = (256,)
-        s["rel_cls_embed.weight"] = (self.num_relations, 256)
-        s["rel_cls_embed.bias"] = (self.num_relations,)
+
+    def _branch_param_shapes(self, s):
+        """The L + 1 class and box branches (shared with det_head.py)."""
+        nc = self.cls_out_channels
         npred = self.num_dec_layers + 1
         for i in range(npred):
             s["cls_branches.%d.weight" % i] = (nc, 256)
@@ -184,7 +203,6 @@ class CrossHeadBBox(CrossHead2):
             for j, n in ((0, 256), (2, 256), (4, 4)):
                 s["reg_branches.%d.%d.weight" % (i, j)] = (n, 256)
                 s["reg_branches.%d.%d.bias" % (i, j)] = (n,)
-        return s
 
     def init_weights(self, seed=0):
         """Random init in the families the reference ends up with (pairnet_bbox_head.py:157-171
@@ -234,6 +252,24 @@ class CrossHeadBBox(CrossHead2):
                                "there is no CPU path")
         hip.lib()
         w = {k: v.to(self.device).contiguous() for k, v in self._params.items()}
+        self._pack_trunk(w)
+        # CrossHead2's relation stage under its own parameter names
+        w["rel_query_embed.weight"] = w["rel_query_pos_embed.weight"]
+        w["rel_query_embed2.weight"] = w["rel_key_pos_embed.weight"]
+        for i in range(self.num_rel_layers):
+            self._pack_vqk(w, "relation_decoder.layers.%d.attentions.1.attn." % i)
+            a = "relation_decoder.layers.%d.attentions.0.attn." % i
+            W, b = w[a + "in_proj_weight"], w[a + "in_proj_bias"]
+            w[a + "vk.weight"] = torch.cat([W[512:], W[256:512]], 0).contiguous()
+            w[a + "vk.bias"] = torch.cat([b[512:], b[256:512]], 0).contiguous()
+        ml = "update_importance.conv_layers."
+        w[ml + "0.0.weight"] = w[ml + "0.0.weight"].reshape(64, 49).contiguous()
+        w[ml + "1.0.weight"] = w[ml + "1.0.weight"].permute(0, 2, 3, 1).reshape(64, -1).contiguous()
+        w[ml + "2.0.weight"] = w[ml + "2.0.weight"].reshape(64, 49).t().contiguous()
+        self.w = w
+
+    def _pack_trunk(self, w):
+        """The Deformable-DETR trunk's packed projections (shared with det_head.py)."""
         t = "transformer."
         for i in range(self.num_enc_layers):
             p = t + "encoder.layers.%d.attentions.0." % i
@@ -250,20 +286,6 @@ class CrossHeadBBox(CrossHead2):
                                             w[a + "attention_weights.weight"]], 0).contiguous()
             w[a + "oa.bias"] = torch.cat([w[a + "sampling_offsets.bias"],
                                           w[a + "attention_weights.bias"]], 0).contiguous()
-        # CrossHead2's relation stage under its own parameter names
-        w["rel_query_embed.weight"] = w["rel_query_pos_embed.weight"]
-        w["rel_query_embed2.weight"] = w["rel_key_pos_embed.weight"]
-        for i in range(self.num_rel_layers):
-            self._pack_vqk(w, "relation_decoder.layers.%d.attentions.1.attn." % i)
-            a = "relation_decoder.layers.%d.attentions.0.attn." % i
-            W, b = w[a + "in_proj_weight"], w[a + "in_proj_bias"]
-            w[a + "vk.weight"] = torch.cat([W[512:], W[256:512]], 0).contiguous()
-            w[a + "vk.bias"] = torch.cat([b[512:], b[256:512]], 0).contiguous()
-        ml = "update_importance.conv_layers."
-        w[ml + "0.0.weight"] = w[ml + "0.0.weight"].reshape(64, 49).contiguous()
-        w[ml + "1.0.weight"] = w[ml + "1.0.weight"].permute(0, 2, 3, 1).reshape(64, -1).contiguous()
-        w[ml + "2.0.weight"] = w[ml + "2.0.weight"].reshape(64, 49).t().contiguous()
-        self.w = w
 
     @staticmethod
     def proposals(shapes, valid_hw=None):
@@ -433,6 +455,25 @@ class CrossHeadBBox(CrossHead2):
     def _layout(self, pl, E, B, shapes, own_tokens):
         """Every per-image buffer as a view of the slot's arena (sizes non-decreasing in B and
         in every level's height / width)."""
+        self._layout_trunk(pl, E, B, shapes, own_tokens)
+        K, nc = self.KEPT, self.cls_out_channels
+        # ---- PPN / relation decoder (CrossHead2's buffers) ----
+        pl.HW2 = 1
+        pl.MP = E(B, K, 1)
+        n_keep = pl.N
+        pl.N = []
+        self._plan_relation(pl, E)
+        pl.N = n_keep
+        pl.scr = E(max(pl.scr.numel(), hip.attn_scratch_floats(B, self.num_proposals,
+                                                                self.num_proposals)))
+        pl.q = E(B * K, 256)
+        R = self.num_rel_query
+        pl.sub_cls, pl.obj_cls = E(B, R, nc), E(B, R, nc)
+        pl.sub_box, pl.obj_box = E(B, R, 4), E(B, R, 4)
+
+    def _layout_trunk(self, pl, E, B, shapes, own_tokens):
+        """The trunk's buffers: encoder, two-stage proposals, decoder, the kept queries (shared
+        with det_head.py)."""
         i64 = E.i64
         pl.B, pl.shapes = B, list(shapes)
         pl.N = [h * wd for h, wd in shapes]
@@ -453,7 +494,7 @@ class CrossHeadBBox(CrossHead2):
         pl.enc_coord, pl.enc_box = E(B, SN, 4), E(B, SN, 4)
         pl.top_idx, pl.top_q, pl.top_r = i64(B, P), i64(B, P), i64(B, P)
         pl.unact = E(B * P, 4)
-        pl.ref = [E(B * P, 4) for _ in range(self.num_dec_layers + 1)]
+        pl.ref = self._layout_refs(pl, E, B * P)
         pl.emb, pl.pt, pl.ptn = E(B * P, 512), E(B * P, 512), E(B * P, 512)
         # ---- decoder ----
         pl.V = [E(B, SN, 256) for _ in range(self.num_dec_layers)]
@@ -463,23 +504,22 @@ class CrossHeadBBox(CrossHead2):
         pl.loc, pl.aw, pl.Sd = E(BP, 8, 4, 4, 2), E(BP, 8, 4, 4), E(BP, 256)
         pl.hd = E(hip.ffn_scratch_floats(BP, self.dec_ffn))
         pl.d1, pl.d2, pl.delta = E(BP, 256), E(BP, 256), E(BP, 4)
-        pl.classes = E(B, P, nc)
+        pl.classes = self._layout_classes(pl, E, B, P, nc)
+        self._layout_kept(pl, E, B, P, K, nc)
+
+    # (three pieces of the trunk's layout that det_head.py carves differently: it returns every
+    # layer's boxes and logits as one tensor each and keeps no query selection)
+    def _layout_refs(self, pl, E, BP):
+        return [E(BP, 4) for _ in range(self.num_dec_layers + 1)]
+
+    def _layout_classes(self, pl, E, B, P, nc):
+        return E(B, P, nc)
+
+    def _layout_kept(self, pl, E, B, P, K, nc):
         pl.qscore = E(B, P)
-        pl.keep, pl.keep_q, pl.keep_r = i64(B, K), i64(B, K), i64(B, K)
+        pl.keep, pl.keep_q, pl.keep_r = E.i64(B, K), E.i64(B, K), E.i64(B, K)
         pl.cls = E(B, K, nc)
         pl.box = E(B, K, 4)
-        # ---- PPN / relation decoder (CrossHead2's buffers) ----
-        pl.HW2 = 1
-        pl.MP = E(B, K, 1)
-        n_keep = pl.N
-        pl.N = []
-        self._plan_relation(pl, E)
-        pl.N = n_keep
-        pl.scr = E(max(pl.scr.numel(), hip.attn_scratch_floats(B, P, P)))
-        pl.q = E(B * K, 256)
-        R = self.num_rel_query
-        pl.sub_cls, pl.obj_cls = E(B, R, nc), E(B, R, nc)
-        pl.sub_box, pl.obj_box = E(B, R, 4), E(B, R, 4)
 
     # ------------------------------------------------------------------ stages
     def _encoder(self, pl):
@@ -595,10 +635,15 @@ class CrossHeadBBox(CrossHead2):
                        self.dec_ffn)
             self._box_branch(i, pl.x, pl, pl.delta)
             hip.box_refine(pl.delta, pl.ref[i], pl.ref[i + 1], B * P)
+            self._layer_outputs(i, pl)
             x_in = pl.x
         nl = self.num_dec_layers
         hip.linear(pl.x, w["cls_branches.%d.weight" % (nl - 1)], w["cls_branches.%d.bias" % (nl - 1)],
                    pl.classes.view(B * P, -1))
+
+    def _layer_outputs(self, i, pl):
+        """Hook behind decoder layer i's box refinement (det_head.py: that layer's class logits);
+        nothing here -- this head reads the last layer only."""
 
     def _select(self, pl):
         """pairnet_bbox_head.py:252-266: rank the queries (softmax over the query axis, max over

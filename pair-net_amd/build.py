@@ -10,7 +10,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libpairnet_hip.so")
-SOURCES = ["gemm", "gemm_ln", "gemm_s3", "stem", "winograd", "ffn", "norm", "msda", "resize", "attn", "ppn", "postproc", "evaluate", "swin", "swin_grad", "preprocess", "augment", "detr", "loss", "assign", "grad", "optim", "dropout", "seg_loss", "panoptic_quality", "rel_loss", "seg_grad", "fpn_grad", "attn_grad", "box_loss", "msda_grad", "tri_loss", "tri_grad", "grouped_conv", "nogc", "train_log"]
+SOURCES = ["gemm", "gemm_ln", "gemm_s3", "stem", "winograd", "ffn", "norm", "msda", "resize", "attn", "ppn", "postproc", "evaluate", "swin", "swin_grad", "preprocess", "augment", "detr", "loss", "assign", "grad", "optim", "dropout", "seg_loss", "panoptic_quality", "rel_loss", "seg_grad", "fpn_grad", "attn_grad", "box_loss", "msda_grad", "tri_loss", "tri_grad", "grouped_conv", "nogc", "train_log", "det_loss"]
 # No packed-fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) anywhere in the
 # library: while waves of the bf16-MFMA GEMM (csrc/gemm_s3.hip: dense MFMAs + LDS-DMA) are
 # resident on a CU, such instructions in OTHER kernels' waves were measured to return wrong

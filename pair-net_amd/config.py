@@ -311,6 +311,70 @@ def pairnet_rnext101_vg():
     return cfg
 
 
+def det_head_cfg(num_query=100, num_classes=150):
+    """The `bbox_head` of configs/deformable_detr/od_r101_vg.py:26-85: mmdet's DeformableDETRHead,
+    two-stage and box-refining, on the trunk `bbox_head_cfg` restates."""
+    trunk = dict(bbox_head_cfg()["transformer"])
+    trunk.pop("as_two_stage", None)      # (od_r101_vg.py: the head hands its own flag down)
+    return ConfigDict(
+        type="DeformableDETRHead", num_query=num_query, num_classes=num_classes, in_channels=2048,
+        sync_cls_avg_factor=True, as_two_stage=True, with_box_refine=True, transformer=trunk,
+        positional_encoding=dict(type="SinePositionalEncoding", num_feats=128, normalize=True,
+                                 offset=-0.5),
+        loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=2.0),
+        loss_bbox=dict(type="L1Loss", loss_weight=5.0),
+        loss_iou=dict(type="GIoULoss", loss_weight=2.0))
+
+
+def det_train_cfg():
+    """`train_cfg` of configs/deformable_detr/od_r101_vg.py:87-94."""
+    return dict(assigner=dict(
+        type="HungarianAssigner", cls_cost=dict(type="FocalLossCost", weight=2.0),
+        reg_cost=dict(type="BBoxL1Cost", weight=5.0, box_format="xywh"),
+        iou_cost=dict(type="IoUCost", iou_mode="giou", weight=2.0)))
+
+
+def det_test_pipeline_cfg():
+    """`test_pipeline` of configs/_base_/datasets/vg_detection.py:27-43 (the od configs' base):
+    pairnet.py's with Pad(size_divisor=32)."""
+    return [
+        dict(type="LoadImageFromFile"),
+        dict(type="MultiScaleFlipAug", img_scale=(1333, 800), flip=False, transforms=[
+            dict(type="Resize", keep_ratio=True),
+            dict(type="RandomFlip"),
+            dict(type="Normalize", **IMG_NORM_CFG),
+            dict(type="Pad", size_divisor=32),
+            dict(type="ImageToTensor", keys=["img"]),
+            dict(type="Collect", keys=["img"]),
+        ]),
+    ]
+
+
+def od_r101_vg():
+    """configs/deformable_detr/od_r101_vg.py:3-96 (the `model` section): the plain detector the box
+    head's trunk is initialised from -- ResNet-101 (C3-C5) -> ChannelMapper -> DeformableDETRHead
+    with 100 queries on Visual Genome's 150 classes."""
+    return ConfigDict(model=dict(
+        type="DeformableDETR",
+        backbone=dict(type="ResNet", depth=101, num_stages=4, out_indices=(1, 2, 3),
+                      frozen_stages=1, norm_cfg=dict(type="BN", requires_grad=False),
+                      norm_eval=True, style="pytorch", with_cp=True),
+        neck=channel_mapper_cfg(), bbox_head=det_head_cfg(num_query=100),
+        train_cfg=det_train_cfg(), test_cfg=dict(max_per_img=100)))
+
+
+def od_rnext101_vg():
+    """configs/deformable_detr/od_rnext101_vg.py (the `model` section): the same detector on
+    ResNeXt-101 32x8d with `num_query=300`."""
+    cfg = od_r101_vg()
+    cfg.model["backbone"] = _to_cfg(dict(
+        type="ResNeXt", depth=101, groups=32, base_width=8, num_stages=4, out_indices=(1, 2, 3),
+        frozen_stages=1, norm_cfg=dict(type="BN", requires_grad=False), norm_eval=True,
+        style="pytorch", with_cp=True))
+    cfg.model["bbox_head"] = det_head_cfg(num_query=300)
+    return cfg
+
+
 def test_pipeline_cfg():
     """`test_pipeline` of configs/mask2former/pairnet.py:310-331 (what preprocess.TestPipeline
     .from_config consumes)."""

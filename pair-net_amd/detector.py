@@ -415,8 +415,7 @@ class PSGTr:
                                       "(pairnet_rnext101_vg.py) and SwinTransformer "
                                       "(pairnet_swinb.py)")
         head_cfg = dict(bbox_head)
-        heads = dict(CrossHead2=CrossHead2, CrossHeadBaseline=CrossHeadBaseline,
-                     PSGTrHead2=PSGTrHead2, CrossHeadBBox=CrossHeadBBox)
+        heads = self._head_types()
         head_type = head_cfg.pop("type", "CrossHead2")
         if head_type not in heads:
             raise NotImplementedError("bbox_head.type must be one of %s" % sorted(heads))
@@ -425,11 +424,18 @@ class PSGTr:
         # CrossHead2, CrossHeadBBox and PSGTrHead2 read it, for their losses)
         self.bbox_head = heads[head_type](**head_cfg,
                                           train_cfg=train_cfg if head_type in (
-                                              "CrossHead2", "CrossHeadBBox", "PSGTrHead2") else None,
+                                              "CrossHead2", "CrossHeadBBox", "PSGTrHead2",
+                                              "DeformableDETRHead") else None,
                                           test_cfg=test_cfg or dict(max_per_img=100))
         self.num_classes = self.bbox_head.num_classes
         self.test_pipeline = None     # built by detect() (or set a preprocess.TestPipeline)
         self._mask_fetch = None       # bit-packed D2H of the masks into recycled arrays
+
+    @staticmethod
+    def _head_types():
+        """bbox_head.type -> class (det_detector.py's DeformableDETR has its own table)."""
+        return dict(CrossHead2=CrossHead2, CrossHeadBaseline=CrossHeadBaseline,
+                    PSGTrHead2=PSGTrHead2, CrossHeadBBox=CrossHeadBBox)
 
     def to(self, device):
         self.__dict__.pop("_pipes", None)     # (cached pipelines hold the old device's streams)
@@ -1179,10 +1185,15 @@ def load_checkpoint(model, filename, map_location="cpu", strict=False, trust=Fal
 def build_detector(cfg, train_cfg=None, test_cfg=None):
     """`build_detector(cfg.model)` (tools/test.py:235-236)."""
     cfg = dict(cfg)
-    if cfg.pop("type", "PSGTr") != "PSGTr":
-        raise NotImplementedError("only type='PSGTr'")
+    kind = cfg.pop("type", "PSGTr")
+    if kind == "DeformableDETR":         # configs/deformable_detr/od_r101_vg.py:3-96
+        from .det_detector import DeformableDETR as cls
+    elif kind == "PSGTr":
+        cls = PSGTr
+    else:
+        raise NotImplementedError("only type='PSGTr' and type='DeformableDETR'")
     model_train_cfg = cfg.pop("train_cfg", None)
-    det = PSGTr(cfg["backbone"], cfg["bbox_head"],
+    det = cls(cfg["backbone"], cfg["bbox_head"],
                 train_cfg=model_train_cfg if model_train_cfg is not None else train_cfg,
                 test_cfg=cfg.get("test_cfg", test_cfg), neck=cfg.get("neck"))
     det.optimizer_cfg = cfg.get("optimizer")      # (optional; read by `trainer()` only)

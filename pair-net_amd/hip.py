@@ -294,6 +294,13 @@ _SIGS = {
     "pn_train_log_row_f32": (C.c_int, [C.POINTER(_vp), _i32, C.c_uint32, _vp, _vp, _vp, _i32, _i32,
                                        _i32, _vp]),
     "pn_train_log_window_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pn_det_match_cost_f32": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64,
+                                        _i64, _i32, _i32] + [_f32] * 7 + [_vp]),
+    "pn_det_focal_partials": (_i64, [_i64, _i32, _i32]),
+    "pn_det_focal_f32": (C.c_int, [_vp] * 6 + [_i64, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _vp]),
+    "pn_det_box_loss_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp,
+                                      _vp, _vp, _f32, _f32, _f32, _vp]),
+    "pn_det_results_f32": (C.c_int, [_vp] * 6 + [_i32] * 5 + [_vp]),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 34  # PN_ABI_VERSION of include/pairnet_hip.h these bindings were written for
@@ -2339,3 +2346,84 @@ def train_log_window(ring, n, T, record):
     assert record.is_contiguous()
     _check(lib().pn_train_log_window_f32(_ptr(ring), ring.shape[0], ring.stride(0), int(n), int(T),
                                          _ptr(record), _stream()), "pn_train_log_window_f32")
+
+
+# ---- the plain Deformable-DETR detector's loss and box results (csrc/det_loss.hip; composed in
+# det_losses.py / det_head.py) ----
+DET_MAX_TERMS = 16      # terms of one pn_det_focal_f32 / pn_det_box_loss_f32 launch
+DET_MAX_G = 1024        # ground-truth boxes of one pn_det_match_cost_f32 problem
+DET_MAX_ROWS = 65536    # rows of one problem
+
+
+def det_match_cost(cls, box, gt_labels, gt_bboxes, factor, tab, cost, max_cells, w_cls=2.0,
+                   w_reg=5.0, w_iou=2.0, alpha=0.25, gamma=2.0, eps=1e-12, iou_eps=1e-6):
+    """include/pairnet_hip.h: pn_box_match_cost_f32's cost for P problems of their own row counts,
+    one launch.  cls [rows, nc] / box [rows, 4]: the problems' rows concatenated; gt_labels [.]
+    int64, gt_bboxes [., 4] fp32 (xyxy, pixels); factor [P, 4]; tab [P, 6] int64 = (cost offset,
+    rows, G, label offset, box offset, row offset); `max_cells`: the largest rows * G of the table
+    (the caller's contract: the table is on the device, and cells past it are not written)."""
+    rows, nc = cls.shape
+    P = tab.shape[0]
+    assert box.shape == (rows, 4) and factor.shape == (P, 4) and tab.shape == (P, 6)
+    assert gt_bboxes.dim() == 2 and gt_bboxes.shape[1] == 4 and gt_labels.dim() == 1
+    assert all(t.is_contiguous() for t in (cls, box, gt_labels, gt_bboxes, factor, tab, cost))
+    _check(lib().pn_det_match_cost_f32(_ptr(cls), _ptr(box), rows, _ptr(gt_labels, torch.int64),
+                                       gt_labels.numel(), _ptr(gt_bboxes), gt_bboxes.shape[0],
+                                       _ptr(factor), _ptr(tab, torch.int64), _ptr(cost),
+                                       cost.numel(), int(max_cells), P, nc, w_cls, w_reg, w_iou,
+                                       alpha, gamma, eps, iou_eps, _stream()),
+           "pn_det_match_cost_f32")
+
+
+def det_focal_partials(rows, C, T):
+    """Floats of pn_det_focal_f32's partial buffer (0: a shape the entry refuses)."""
+    return int(lib().pn_det_focal_partials(int(rows), int(C), int(T)))
+
+
+def det_focal(x, labels, term, avg, grad, partial, out, w_cls=2.0, alpha=0.25, gamma=2.0):
+    """include/pairnet_hip.h: the focal term of every loss term in one launch over the concatenated
+    rows.  x / grad [rows, C]; labels / term [rows] int32 (label C = background); avg [T] the
+    terms' factors; out [T] = w_cls * sum / avg; grad = (w_cls / avg[term]) d loss / d x."""
+    rows, C = x.shape
+    T = avg.numel()
+    assert grad.shape == x.shape and labels.shape == (rows,) and term.shape == (rows,)
+    assert out.numel() == T
+    assert all(t.is_contiguous() for t in (x, labels, term, avg, grad, partial, out))
+    _check(lib().pn_det_focal_f32(_ptr(x), _ptr(labels, torch.int32), _ptr(term, torch.int32),
+                                  _ptr(avg), _ptr(grad), _ptr(partial), partial.numel(), _ptr(out),
+                                  rows, C, T, w_cls, alpha, gamma, _stream()), "pn_det_focal_f32")
+
+
+def det_box_loss(box, gt_bboxes, factor, pairs, term_off, avg, grad, out, w_bbox=5.0, w_iou=2.0,
+                 iou_eps=1e-6):
+    """include/pairnet_hip.h: the L1 and GIoU terms over the matched pairs, one workgroup per term.
+    box / grad [rows, 4] (grad zeroed by the caller); gt_bboxes [., 4]; factor [F, 4]; pairs [M, 4]
+    int32 = (row, ground-truth box, factor row, term) grouped by term; term_off [T + 1] int32;
+    out [T, 2] = (loss_bbox, loss_iou)."""
+    rows, T, M = box.shape[0], avg.numel(), 0 if pairs is None else pairs.shape[0]
+    assert box.shape == (rows, 4) == grad.shape and factor.dim() == 2 and factor.shape[1] == 4
+    assert term_off.numel() == T + 1 and out.shape == (T, 2)
+    assert M == 0 or (pairs.shape == (M, 4) and gt_bboxes.dim() == 2 and gt_bboxes.shape[1] == 4)
+    ts = [t for t in (box, gt_bboxes, factor, pairs, term_off, avg, grad, out) if t is not None]
+    assert all(t.is_contiguous() for t in ts)
+    nb = 0 if gt_bboxes is None else gt_bboxes.shape[0]
+    _check(lib().pn_det_box_loss_f32(_ptr(box), rows, _ptr(gt_bboxes) if nb else None, nb,
+                                     _ptr(factor), factor.shape[0],
+                                     _ptr(pairs, torch.int32) if M else None,
+                                     _ptr(term_off, torch.int32), M, T, _ptr(avg), _ptr(grad),
+                                     _ptr(out), w_bbox, w_iou, iou_eps, _stream()),
+           "pn_det_box_loss_f32")
+
+
+def det_results(cls, box, idx, meta, det, labels, rescale):
+    """include/pairnet_hip.h: ranked flat indices idx [B, K] into cls [B, Q, C] -> det [B, K, 5]
+    (clamped, optionally rescaled xyxy + sigmoid score) and labels [B, K] int64; meta [B, 6] =
+    (img_h, img_w, scale_factor[0..3])."""
+    B, Q, C = cls.shape
+    K = idx.shape[1]
+    assert box.shape == (B, Q, 4) and idx.shape == (B, K) and meta.shape == (B, 6)
+    assert det.shape == (B, K, 5) and labels.shape == (B, K)
+    assert all(t.is_contiguous() for t in (cls, box, idx, meta, det, labels))
+    _check(lib().pn_det_results_f32(_ptr(cls), _ptr(box), _ptr(idx, torch.int64), _ptr(meta),
+                                    _ptr(det), _ptr(labels, torch.int64), B, Q, C, K,
+                                    1 if rescale else 0, _stream()), "pn_det_results_f32")
