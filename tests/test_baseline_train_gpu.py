@@ -32,7 +32,7 @@ def _head(sd):
     return head
 
 
-def _batch():
+def _batch(H=H, W=W):
     gen = torch.Generator().manual_seed(8)
     gt_labels = [torch.randint(0, 133, (n,), generator=gen) for n in COUNTS]
     gt_masks = [(torch.rand(n, H // 2, W // 2, generator=gen) > 0.6).to(torch.uint8) for n in COUNTS]
@@ -42,16 +42,17 @@ def _batch():
     return metas, gt_rels, gt_labels, gt_masks
 
 
-def _first_step(scope):
+def _first_step(scope, hw=(H, W)):
     """One `step` of a fresh trainer beside the twin's statement; cached per scope ("feats": the
     four feature maps, backbone frozen; "image": ResNet stages 2-4 trained, from the image)."""
-    if scope in _S:
-        return _S[scope]
+    key, (H, W) = (scope, hw), hw
+    if key in _S:
+        return _S[key]
     assert torch.cuda.is_available(), "-m gpu tests need the MI355X"
     from pairnet_amd import BackboneGrad, BaselineTrainer, ResNet50Hip
     _, sd, _ = oracle_baseline_head(1234)
     twin, head = _head(sd), _head(sd)
-    metas, gt_rels, gt_labels, gt_masks = _batch()
+    metas, gt_rels, gt_labels, gt_masks = _batch(H, W)
     bb = bb_twin = None
     if scope == "image":
         bb = ResNet50Hip().to(DEV)
@@ -84,16 +85,19 @@ def _first_step(scope):
     out = tr.step(x, metas, gt_rels, gt_labels, gt_masks)
     torch.cuda.synchronize()
     out = {k: v.clone() for k, v in out.items()}
-    _S[scope] = dict(tr=tr, head=head, bb=bb, sd=sd, x=x, p0=p0, out=out, losses_t=losses_t,
+    _S[key] = dict(tr=tr, head=head, bb=bb, sd=sd, x=x, p0=p0, out=out, losses_t=losses_t,
                      grads_t=grads_t, flat_grad=tr.flat_grad.clone(), flat_p1=tr.flat_p.clone(),
                      before=before, bb_before=bb_before, ends=list(tr.last_ready_ends))
-    return _S[scope]
+    return _S[key]
 
 
 @pytest.mark.parametrize("scope", ["feats", "image"])
 def test_step_losses_and_gradients_are_the_twins(scope):
+    _check_twins(_first_step(scope), scope)
+
+
+def _check_twins(s, scope):
     from pairnet_amd import BaselineHeadGrad, SegPixelDecoderGrad
-    s = _first_step(scope)
     tr, out = s["tr"], s["out"]
     assert set(out) == set(s["losses_t"]) | {"grad_norm", "assign_status"} and len(s["losses_t"]) == 30
     for k, v in s["losses_t"].items():

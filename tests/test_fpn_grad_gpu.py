@@ -18,6 +18,8 @@ from test_seg_grad_gpu import COUNTS, _oracle64, _train_cfg, _trunk_names
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 PYRAMIDS = [(64, 96), (52, 76)]
+ODD_BATCH = (72, 100)                   # tests/grad_shapes.py B: 18 x 25 over 9 x 13, THREE images
+BATCH = {ODD_BATCH: 3}
 _S = {}
 
 
@@ -40,9 +42,10 @@ def _run(H, W):
     if (H, W) not in _S:
         from pairnet_amd import SegPixelDecoderGrad
         head, sd = _head()
-        feats = seeded.seeded_feats(99, 2, H, W)
+        bs = BATCH.get((H, W), 2)
+        feats = seeded.seeded_feats(99, bs, H, W)
         dfe = [f.to(DEV) for f in feats]
-        metas = [dict(img_shape=(H, W, 3), scale_factor=[1.5] * 4)] * 2
+        metas = [dict(img_shape=(H, W, 3), scale_factor=[1.5] * 4)] * bs
         cls, masks = head.forward(dfe, metas)
         torch.cuda.synchronize()
         pl = head._last_plan
@@ -50,24 +53,24 @@ def _run(H, W):
         mem, MF = tape.forward(dfe)
         torch.cuda.synchronize()
         g = torch.Generator().manual_seed(H + W)
-        _S[(H, W)] = dict(feats=feats, dfe=dfe, pl=pl, plMF=pl.MF.view(2, pl.HW2, 256).clone(),
+        _S[(H, W)] = dict(feats=feats, dfe=dfe, pl=pl, plMF=pl.MF.view(bs, pl.HW2, 256).clone(),
                           plX=pl.X.clone(), cls=cls, masks=masks, tape=tape, mem=mem, MF=MF,
                           G_mem=torch.randn(tuple(mem.shape), generator=g).to(DEV),
                           G_MF=torch.randn(tuple(MF.shape), generator=g).to(DEV))
     return _S[(H, W)]
 
 
-def _reference(H, W):
+def _reference(H, W, dtype=torch.float64):
     """Float64 autograd of <MF, G_MF> and of sum_l <outs_l, G_mem,l> through the oracle's pixel
     decoder, separately (the functional is linear in the pair): -> dict(mem, MF: lists of the four
     feature gradients + {parameter name: gradient}; z: the statement's pre-ReLU map)."""
-    key = ("ref", H, W)
+    key = ("ref", H, W) if dtype == torch.float64 else ("ref", H, W, dtype)
     if key not in _S:
         head, sd = _head()
         s = _run(H, W)
-        head_o = _oracle64(sd)
+        head_o = _oracle64(sd).to(dtype)    # (fp32: the oracle's own miss, for `_compare`'s `e32`)
         pd = head_o.pixel_decoder
-        f64 = [f.double().requires_grad_() for f in s["feats"]]
+        f64 = [f.to(dtype).requires_grad_() for f in s["feats"]]
         _, memories = pd(f64)
         mem_ref = torch.cat([m.flatten(2).transpose(1, 2) for m in memories], 1)
         Y = s["tape"].t["fpn"]["Y"]                                  # [B, H2, W2, 256], post-ReLU
@@ -78,8 +81,8 @@ def _reference(H, W):
         params = [dict(head_o.named_parameters())[n] for n in names]
         out = dict(z=z.detach(), gate=gate, mem_val=mem_ref.detach(), MF_val=MFr.detach(),
                    names=names, head_o=head_o)
-        for k, loss in (("mem", (mem_ref * s["G_mem"].cpu().double()).sum()),
-                        ("MF", (MFr * s["G_MF"].cpu().double()).sum())):
+        for k, loss in (("mem", (mem_ref * s["G_mem"].cpu().to(dtype)).sum()),
+                        ("MF", (MFr * s["G_MF"].cpu().to(dtype)).sum())):
             gs = torch.autograd.grad(loss, f64 + params, retain_graph=True, allow_unused=True)
             out[k] = ([g for g in gs[:4]], dict(zip(names, gs[4:])))
         _S[key] = out
@@ -92,22 +95,38 @@ def _sum(a, b):
     return a + b
 
 
-def _check(H, W, dfeats, grads, parts, report):
-    """`parts`: which of the reference's two halves the upstream gradients contained."""
-    ref = _reference(H, W)
+def _parts(ref, parts):
     fg, pg = [None] * 4, {n: None for n in ref["names"]}
     for k in parts:
         fg = [_sum(a, b) for a, b in zip(fg, ref[k][0])]
         pg = {n: _sum(pg[n], ref[k][1][n]) for n in pg}
+    return fg, pg
+
+
+def _check(H, W, dfeats, grads, parts, report, need_dc2=True, fp32_rule=False):
+    """`parts`: which of the reference's two halves the upstream gradients contained.  `fp32_rule`:
+    bounds by the oracle's own fp32 run (tests/test_grad_gpu.py `_compare`, `e32`)."""
+    ref = _reference(H, W)
+    fg, pg = _parts(ref, parts)
+    e32 = None
+    if fp32_rule:
+        from test_grad_gpu import _fp32_miss
+        fg32, pg32 = _parts(_reference(H, W, torch.float32), parts)
+        named = lambda f, p: dict({"features of level %d" % l: f[3 - l] for l in range(3)},
+                                  **{"features C2": f[0]}, **{n: v for n, v in p.items() if v is not None})
+        e32 = _fp32_miss(named(fg, pg), named(fg32, pg32))
     for l in range(3):
-        _compare("features of level %d" % l, dfeats[l], fg[3 - l], report)
-    _compare("features C2", dfeats[3], fg[0], report)
+        _compare("features of level %d" % l, dfeats[l], fg[3 - l], report, e32)
+    if need_dc2:
+        _compare("features C2", dfeats[3], fg[0], report, e32)
+    else:
+        assert dfeats[3] is None and len(dfeats) == 4
     head_o = ref["head_o"]
     for n, p in head_o.named_parameters():
         p.grad = pg.get(n)
     names = [n for n in ref["names"] if pg[n] is not None]
     assert len(ref["names"]) == 117
-    _compare_params(grads, head_o, report, names)
+    _compare_params(grads, head_o, report, names, e32)
     return names
 
 
@@ -155,6 +174,27 @@ def test_backward_against_float64_autograd(H, W, algo):
     assert ends == sorted(ends) and ends[-1] == tape.flat_numel == tape.size_of(_head()[0])
     assert ends[:3] == [tape.group_end[g] for g in ("mask_feature", "output_convs.0",
                                                     "lateral_convs.0")]
+
+
+@pytest.mark.parametrize("need_dc2", [True, False])
+def test_backward_on_three_images_of_72x100(need_dc2):
+    """The taped forward and the backward at 18 x 25 over 9 x 13, 5 x 7, 3 x 4 with a batch of
+    three: 1 350 C2 rows (no multiple of 64), 164 encoder tokens (no multiple of 32), a 25-wide mask
+    feature; with and without d C2."""
+    H, W = ODD_BATCH
+    s = _run(H, W)
+    ref = _reference(H, W)
+    assert s["pl"].B == 3 and tuple(s["pl"].hw2) == (18, 25) and s["mem"].shape[1] == 164
+    assert float((s["MF"] - s["plMF"]).abs().max()) < 1e-4
+    assert float((s["mem"].cpu().double() - ref["mem_val"]).abs().max()) < 1e-4
+    assert R.gate_mismatch(ref["gate"], ref["z"]) <= R.GATE_CAP
+    assert float((s["MF"].cpu().double() - ref["MF_val"]).abs().max()) < 1e-4
+    dfeats, grads = s["tape"].backward(s["G_mem"], s["G_MF"], need_dc2=need_dc2)
+    torch.cuda.synchronize()
+    report = []
+    names = _check(H, W, dfeats, grads, ("mem", "MF"), report, need_dc2=need_dc2, fp32_rule=True)
+    assert len(names) == 117 and sorted(names) == sorted(grads)
+    _print(report)
 
 
 def _same_walk(dfeats, grads, ref_dfeats, ref_grads, report):

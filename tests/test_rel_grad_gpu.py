@@ -17,7 +17,7 @@ import rel_grad_ref as RR
 import seg_grad_ref as R
 from helpers import baseline_cfg, oracle_baseline_head
 from oracle import seeded
-from test_grad_gpu import _compare, _compare_params, _print, _unpack_mask
+from test_grad_gpu import _compare, _compare_params, _fp32_miss, _print, _unpack_mask
 from test_seg_grad_gpu import COUNTS, _oracle64, _random_grads, _train_cfg, _trunk_names
 
 pytestmark = pytest.mark.gpu
@@ -94,11 +94,11 @@ class _FixedDrop(torch.nn.Module):
         return x * self.mult
 
 
-def _reference(tape, pl, sd, grads, drop=None):
+def _reference(tape, pl, sd, grads, drop=None, dtype=torch.float64):
     """Float64 autograd of the linear functional the six gradients define, through the oracle's
     nine masked layers (under the tape's mask bits), the statement's heads and the relation stage
     -> (d mem, d MF, oracle head with .grad, (rel, sub, obj) values)."""
-    head_o = _oracle64(sd)
+    head_o = _oracle64(sd).to(dtype)        # (`dtype`: fp32 for the oracle's own miss, `_fp32_miss`)
     B, Q = pl.B, tape.Q
     if drop is not None:
         s = float(dropout_ref.scale(drop.p))
@@ -114,8 +114,8 @@ def _reference(tape, pl, sd, grads, drop=None):
                             .double() * s)
             ffn.layers[0][2] = _FixedDrop(mult[0])
             ffn.layers[2] = _FixedDrop(mult[1])
-    mem = pl.X.cpu().double().requires_grad_()
-    MF = pl.MF.view(B, pl.HW2, 256).cpu().double().requires_grad_()
+    mem = pl.X.cpu().to(dtype).requires_grad_()
+    MF = pl.MF.view(B, pl.HW2, 256).cpu().to(dtype).requires_grad_()
     keys, key_pos = RR.keys_of(head_o, mem, pl.shapes, pl.start, pl.N)
     q = head_o.query_feat.weight.unsqueeze(1).repeat((1, B, 1))
     q_pos = head_o.query_embed.weight.unsqueeze(1).repeat((1, B, 1))
@@ -130,20 +130,27 @@ def _reference(tape, pl, sd, grads, drop=None):
         qs.append(q.transpose(0, 1))
     cls, mask, _ = R.heads(torch.stack(qs), MF, dict(head_o.named_parameters()))
     rel, sub, obj = RR.relation_stage(head_o, mem, qs[-1], pl.shapes, pl.start, pl.N)
-    d = lambda k: grads[k].cpu().double()
+    d = lambda k: grads[k].cpu().to(dtype)
     total = R.functional(cls, mask, d("cls"), d("mask"), grads["mask_rows"].cpu()) + \
         RR.functional(rel, sub, obj, d("rel"), d("subject_scores"), d("object_scores"))
     total.backward()
     return mem.grad, MF.grad, head_o, (rel.detach(), sub.detach(), obj.detach())
 
 
-def _compare_all(pl, dmem, dMF, g, ref, report, names):
+def _compare_all(pl, dmem, dMF, g, ref, report, names, ref32=None):
+    """`ref32`: `_reference(..., dtype=torch.float32)` -- the bounds then follow `_compare`'s `e32`."""
     dmem_ref, dMF_ref, head_o = ref[:3]
+    lv = lambda t: {"memory tokens of level %d" % l: t[:, pl.start[l]:pl.start[l] + pl.N[l]]
+                    for l in range(3)}
+    e32 = None
+    if ref32 is not None:
+        e32 = _fp32_miss(dict(lv(dmem_ref), **{"mask feature": dMF_ref}),
+                         dict(lv(ref32[0]), **{"mask feature": ref32[1]}), head_o, ref32[2])
     for l in range(3):
         a, b = pl.start[l], pl.start[l] + pl.N[l]
-        _compare("memory tokens of level %d" % l, dmem[:, a:b], dmem_ref[:, a:b], report)
-    _compare("mask feature", dMF, dMF_ref, report)
-    _compare_params(g, head_o, report, names)
+        _compare("memory tokens of level %d" % l, dmem[:, a:b], dmem_ref[:, a:b], report, e32)
+    _compare("mask feature", dMF, dMF_ref, report, e32)
+    _compare_params(g, head_o, report, names, e32)
 
 
 def test_taped_forward_equals_the_plans_relation_outputs():

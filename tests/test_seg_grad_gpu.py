@@ -85,20 +85,21 @@ def _oracle64(sd):
     return head.double()
 
 
-def _reference(tape, pl, sd, grads):
+def _reference(tape, pl, sd, grads, dtype=torch.float64):
     """Float64 autograd of the linear functional through the oracle's nine decoder layers (under the
-    tape's mask bits) and the statement's heads -> (d mem, d MF, oracle head with .grad)."""
-    head_o = _oracle64(sd)
+    tape's mask bits) and the statement's heads -> (d mem, d MF, oracle head with .grad).  `dtype`:
+    the same graph in fp32, for the oracle's own miss (tests/test_grad_gpu.py `_fp32_miss`)."""
+    head_o = _oracle64(sd).to(dtype)
     B, Q = pl.B, tape.Q
-    mem = pl.X.cpu().double().requires_grad_()
-    MF = pl.MF.view(B, pl.HW2, 256).cpu().double().requires_grad_()
+    mem = pl.X.cpu().to(dtype).requires_grad_()
+    MF = pl.MF.view(B, pl.HW2, 256).cpu().to(dtype).requires_grad_()
     keys, key_pos = [], []
     for l in range(3):
         h, w = pl.shapes[l]
         m = mem[:, pl.start[l]:pl.start[l] + pl.N[l]].transpose(0, 1)
         keys.append(m + head_o.level_embed.weight[l].view(1, 1, -1))
         pad = torch.zeros((B, h, w), dtype=torch.bool)
-        key_pos.append(head_o.decoder_positional_encoding(pad).flatten(2).permute(2, 0, 1).double())
+        key_pos.append(head_o.decoder_positional_encoding(pad).flatten(2).permute(2, 0, 1).to(dtype))
     q = head_o.query_feat.weight.unsqueeze(1).repeat((1, B, 1))
     q_pos = head_o.query_embed.weight.unsqueeze(1).repeat((1, B, 1))
     qs = []
@@ -111,7 +112,7 @@ def _reference(tape, pl, sd, grads):
                   attn_masks=[mask, None], query_key_padding_mask=None, key_padding_mask=None)
         qs.append(q.transpose(0, 1))
     cls, mask, _ = R.heads(torch.stack(qs), MF, dict(head_o.named_parameters()))
-    R.functional(cls, mask, grads["cls"].cpu().double(), grads["mask"].cpu().double(),
+    R.functional(cls, mask, grads["cls"].cpu().to(dtype), grads["mask"].cpu().to(dtype),
                  grads["mask_rows"].cpu()).backward()
     return mem.grad, MF.grad, head_o
 

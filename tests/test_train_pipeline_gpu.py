@@ -213,9 +213,12 @@ def test_batch_reuses_its_slot_and_reports_a_crop_without_relations():
 
 
 def test_detector_train_step_takes_the_batch():
-    """`det.train_step(pipe.batch(...), None)` on the R50 detector: finite loss terms and
-    grad_norm; the marker-wrapped masks and the staged full-size masks give identical prepared
-    tensors (the tensors are compared, not a second optimizer trajectory)."""
+    """`det.train_step(pipe.batch(...), None)` on the R50 detector, an odd 112 x 154 batch tensor
+    (C2 28 x 39 over 14 x 20, 7 x 10, 4 x 5): finite loss terms and grad_norm, and their VALUES --
+    each loss term against the oracle loss on the same batch, grad_norm against the norm of the
+    float64 gradient; the marker-wrapped masks and the staged full-size masks give identical
+    prepared tensors (the tensors are compared, not a second optimizer trajectory).  The gradient
+    itself is compared tensor by tensor at 61 x 87 in tests/test_train_shapes_gpu.py."""
     from pairnet_amd import build_detector, pairnet_r50
     det = build_detector(pairnet_r50())
     det.bbox_head.init_weights(seed=4)
@@ -230,11 +233,45 @@ def test_detector_train_step_takes_the_batch():
     a = det._prepare_gt_masks(batch["img"], batch["gt_masks"])
     b = det._prepare_gt_masks(batch["img"], [s["masks"] for s in staged])
     assert all(torch.equal(x, y) and bool(x.any()) for x, y in zip(a, b))
+    # what the step will see, kept before any parameter moves (for the value checks below)
+    head, bb = det.bbox_head, det.backbone
+    cpu = lambda d: {k: v.detach().cpu().clone() for k, v in d.items()}
+    sd_head, sd_bb = cpu(head.state_dict()), cpu(bb.state_dict())
+    feats = [f.clone(memory_format=torch.preserve_format) for f in bb(batch["img"])]
+    assert [tuple(f.shape[-2:]) for f in feats] == [(28, 39), (14, 20), (7, 10), (4, 5)]
+    outs = tuple(cpu(d) for d in head.forward(feats, batch["img_metas"]))
+    torch.cuda.manual_seed(77)                   # the loss draws its mask points from this generator
     rec = det.train_step(batch, None)
     assert set(rec) == {"loss", "log_vars", "num_samples"} and rec["num_samples"] == 2
     terms = {k: v for k, v in rec["log_vars"].items()}
     assert {"loss_r_cls", "loss_sub_cls", "loss_obj_cls", "loss_match", "grad_norm"} <= set(terms)
     assert all(np.isfinite(v) for v in terms.values()) and terms["grad_norm"] > 0
+    # ---- values: the loss terms against the oracle loss on the step's own outputs, prepared masks
+    # and mask points (the bound of tests/test_losses_gpu.py), and grad_norm against the norm of the
+    # float64 gradient of tests/test_train_shapes_gpu.py's graph (ResNet stages 2-4, pixel decoder,
+    # masked decoder, tail, loss) -- within what a 1e-4-of-its-largest-entry error in every entry
+    # of every tensor (the tapes' comparator, tests/test_grad_gpu.py) moves the norm by
+    from oracle.losses import OracleCrossHead2Loss
+    from test_grad_gpu import TOL
+    from test_train_shapes_gpu import oracle_step
+    torch.cuda.manual_seed(77)
+    pts = [torch.rand((1, 12544, 2), device=DEV).cpu() for _ in range(2)]
+    gt_rels = [r.cpu().long() for r in batch["gt_rels"]]
+    gt_labels = [l.cpu().long() for l in batch["gt_labels"]]
+    prepared = [m.cpu() for m in a]
+    want = OracleCrossHead2Loss().loss(outs[0], outs[1], gt_rels, gt_labels, prepared,
+                                       point_coords=pts)
+    for k, v in want.items():
+        print("%-14s HIP %.6f  oracle %.6f" % (k, terms[k], float(v)))
+        assert abs(terms[k] - float(v)) < 1e-4 * max(1.0, abs(float(v))), k
+    tr = det._trainer
+    ref, _, _ = oracle_step(torch.float64, sd_head, sd_bb, feats[0], head._last_plan, tr.tape, outs,
+                            (None, gt_rels, gt_labels, prepared, pts))
+    norm = float(torch.cat([ref[n].reshape(-1) for n in tr.names]).norm())
+    slack = float(np.sqrt(sum(ref[n].numel() * (TOL * float(ref[n].abs().max())) ** 2
+                              for n in tr.names)))
+    print("grad_norm: HIP %.6f, float64 %.6f (allowed %.2e)" % (terms["grad_norm"], norm, slack))
+    assert abs(terms["grad_norm"] - norm) <= slack
 
 
 def test_bad_arguments_are_refused_without_a_launch():

@@ -85,7 +85,7 @@ def _setup():
 def _random_grads(pl, counts, seed, fail=()):
     """Random upstream gradients in the loss's compact form; `fail`: images whose rows are -1 and
     whose mask-gradient rows hold NaN (they must not be read)."""
-    B, Q = 2, 100
+    B, Q = len(counts), 100
     g = torch.Generator().manual_seed(seed)
     grads = dict(sub=torch.randn(1, B, Q, 134, generator=g), obj=torch.randn(1, B, Q, 134, generator=g),
                  rel=torch.randn(1, B, Q, 57, generator=g))
@@ -105,22 +105,25 @@ def _random_grads(pl, counts, seed, fail=()):
     return grads
 
 
-def _reference(tape, pl, sd, grads):
+def _reference(tape, pl, sd, grads, dtype=torch.float64, tape_gates=None):
     """Float64 autograd of the functional through the oracle's nine decoder layers (under the
     tape's mask bits) and the statement's heads -> (d mem, d MF, oracle head with .grad)."""
     head_o = OraclePSGTrHead2(**psgtr2_cfg()).eval()
     head_o.load_state_dict({k: v.detach().cpu() for k, v in sd.items()}, strict=True)
-    head_o = head_o.double()
+    head_o = head_o.to(dtype)               # (`dtype`: fp32 for the oracle's own miss, `_fp32_miss`)
     B, Q = pl.B, tape.Q
-    mem = pl.X.cpu().double().requires_grad_()
-    MF = pl.MF.view(B, pl.HW2, 256).cpu().double().requires_grad_()
+    if tape_gates is not None:              # a list: the FFN ReLUs under the tape's gates, flips noted
+        from test_grad_gpu import _use_tape_ffn_gates
+        _use_tape_ffn_gates(head_o, tape, B, Q, tape_gates)
+    mem = pl.X.cpu().to(dtype).requires_grad_()
+    MF = pl.MF.view(B, pl.HW2, 256).cpu().to(dtype).requires_grad_()
     keys, key_pos = [], []
     for l in range(3):
         h, w = pl.shapes[l]
         m = mem[:, pl.start[l]:pl.start[l] + pl.N[l]].transpose(0, 1)
         keys.append(m + head_o.level_embed.weight[l].view(1, 1, -1))
         pad = torch.zeros((B, h, w), dtype=torch.bool)
-        key_pos.append(head_o.decoder_positional_encoding(pad).flatten(2).permute(2, 0, 1).double())
+        key_pos.append(head_o.decoder_positional_encoding(pad).flatten(2).permute(2, 0, 1).to(dtype))
     q = head_o.query_feat.weight.unsqueeze(1).repeat((1, B, 1))
     q_pos = head_o.query_embed.weight.unsqueeze(1).repeat((1, B, 1))
     for i, layer in enumerate(head_o.transformer_decoder.layers):
@@ -131,7 +134,7 @@ def _reference(tape, pl, sd, grads):
         q = layer(query=q, key=keys[l], value=keys[l], query_pos=q_pos, key_pos=key_pos[l],
                   attn_masks=[mask, None], query_key_padding_mask=None, key_padding_mask=None)
     out = R.heads(q.transpose(0, 1), head_o.query_feat.weight, MF, dict(head_o.named_parameters()))
-    c = lambda k: grads[k].cpu().double()
+    c = lambda k: grads[k].cpu().to(dtype)
     R.functional(out, c("sub"), c("obj"), c("rel"), c("sub_mask"), c("obj_mask"),
                  grads["mask_rows"].cpu()).backward()
     return mem.grad, MF.grad, head_o

@@ -30,7 +30,7 @@ def _head(sd):
     return head
 
 
-def _batch():
+def _batch(H=H, W=W):
     gen = torch.Generator().manual_seed(8)
     gt_labels = [torch.randint(0, 133, (n,), generator=gen) for n in OBJECTS]
     gt_masks = [(torch.rand(n, H // 2, W // 2, generator=gen) > 0.6).to(torch.uint8) for n in OBJECTS]
@@ -40,17 +40,18 @@ def _batch():
     return metas, gt_rels, gt_labels, gt_masks
 
 
-def _first_step(scope, deterministic=False):
+def _first_step(scope, deterministic=False, hw=(H, W)):
     """One `step` of a fresh trainer beside the twin's statement; cached per scope ("feats": the
     four feature maps, backbone frozen; "image": ResNet stages 2-4 trained, from the image)."""
-    key = (scope, deterministic)
+    key = (scope, deterministic, hw)
+    H, W = hw
     if key in _S:
         return _S[key]
     assert torch.cuda.is_available(), "-m gpu tests need the MI355X"
     from pairnet_amd import BackboneGrad, PSGTr2Trainer, ResNet50Hip
     _, sd, _ = oracle_psgtr2_head(1234)
     twin, head = _head(sd), _head(sd)
-    metas, gt_rels, gt_labels, gt_masks = _batch()
+    metas, gt_rels, gt_labels, gt_masks = _batch(H, W)
     bb = bb_twin = None
     if scope == "image":
         bb = ResNet50Hip().to(DEV)
@@ -91,8 +92,11 @@ def _first_step(scope, deterministic=False):
 
 @pytest.mark.parametrize("scope,deterministic", [("feats", False), ("image", False), ("feats", True)])
 def test_step_losses_and_gradients_are_the_twins(scope, deterministic):
+    _check_twins(_first_step(scope, deterministic), scope, deterministic)
+
+
+def _check_twins(s, scope, deterministic):
     from pairnet_amd import PSGTr2HeadGrad, SegPixelDecoderGrad
-    s = _first_step(scope, deterministic)
     tr, out = s["tr"], s["out"]
     assert set(out) == set(s["losses_t"]) | {"grad_norm", "assign_status"} and len(s["losses_t"]) == 7
     for k, v in s["losses_t"].items():
