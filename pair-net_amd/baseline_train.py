@@ -49,7 +49,7 @@ from . import hip
 from .flat_trainer import (FPN_CONV, FlatTrainer, refresh_encoder, refresh_fpn_conv,
                            refresh_key_positions, refresh_q0, refresh_query_positions, refresh_r0,
                            refresh_resnet, refresh_self_attention)
-from .grad import BackboneGrad
+from .backbone_grad import BackboneGrad
 from .seg_grad import BaselineHeadGrad, SegPixelDecoderGrad
 
 __all__ = ["BaselineTrainer"]

@@ -1793,7 +1793,7 @@ def dropout_keep(n, p, seed, subseq, step, site, device=None):
     return keep
 
 
-# ---- Swin backbone backward (csrc/swin_grad.hip; composed in grad.py SwinBackboneGrad) ----------
+# ---- Swin backbone backward (csrc/swin_grad.hip; composed in backbone_grad.py) ---------------
 def layernorm_rows_bwd(dy, x, gamma, dx, gxhat, eps=1e-5):
     """LayerNorm backward over 2-D row views of any width C % 4 == 0, C <= 3072, from the saved
     input x: dx, and gxhat = dy * xhat (its column sum is d weight; d bias: column sum of dy)."""

@@ -45,7 +45,7 @@ from .baseline_train import CUSTOM_KEYS, BaselineTrainer
 from .flat_trainer import (FPN_CONV, FlatTrainer, refresh_encoder, refresh_fpn_conv,
                            refresh_key_positions, refresh_q0, refresh_query_positions,
                            refresh_resnet, refresh_self_attention)
-from .grad import BackboneGrad
+from .backbone_grad import BackboneGrad
 from .seg_grad import PSGTr2HeadGrad, SegPixelDecoderGrad
 
 __all__ = ["PSGTr2Trainer"]

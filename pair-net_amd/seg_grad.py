@@ -42,7 +42,8 @@ both), `reduce_mean` across ranks.
 import torch
 
 from . import hip
-from .grad import HeadGrad, PixelDecoderGrad, RelationTailGrad
+from .grad import HeadGrad, RelationTailGrad
+from .pixel_grad import PixelDecoderGrad
 
 __all__ = ["SegmenterHeadGrad", "BaselineHeadGrad", "PSGTr2HeadGrad", "SegPixelDecoderGrad"]
 
@@ -265,7 +266,6 @@ class SegmenterHeadGrad(HeadGrad):
         N, M, P = L * B * Q, int(rows.shape[0]), pl.HW2
         nc = head.num_classes + 1
         ready = on_ready if on_ready is not None else (lambda end: None)
-        zeros = lambda *s_: torch.zeros(*s_, device=self.dev, dtype=torch.float32)
         grads_out = self._zero_grads()
         me = st["mlp"][2]
         # ---- the mask logits' two products on the compact rows ----
@@ -282,24 +282,17 @@ class SegmenterHeadGrad(HeadGrad):
             dme_all = E(N, 256)
             hip.scatter_rows_add(dme, rows, dme_all, 1, N, M, 256)
         else:
-            dme_all = zeros(N, 256)
+            dme_all = self._zeros(N, 256)
         # ---- mask_embed, cls_embed, post_norm on all rows ----
         dqn = self._mlp3_bwd(dme_all, st["qn"], st["mlp"], "mask_embed", grads_out)
-        ncp = (nc + 3) // 4 * 4           # the GEMMs contract over multiples of 4: zero columns
-        dcls = zeros(N, ncp)
-        dcls[:, :nc].copy_(g_cls.view(N, nc))
-        Wp = zeros(ncp, 256)
-        Wp[:nc].copy_(w["cls_embed.weight"])
-        gp = {"W": zeros(ncp, 256), "b": zeros(ncp)}
-        self._acc(dqn, self._lin_bwd(dcls, st["qn"], Wp, gp, "W", "b"))
-        self._acc(grads_out["cls_embed.weight"], gp["W"][:nc])
-        self._acc(grads_out["cls_embed.bias"], gp["b"][:nc])
+        self._acc(dqn, self._lin_bwd(g_cls.view(N, nc), st["qn"], w["cls_embed.weight"], grads_out,
+                                     "cls_embed.weight", "cls_embed.bias"))
         dq_all = self._ln_bwd(dqn, st["q"], "transformer_decoder.post_norm.", grads_out)
         self.dq_all = dq_all.view(L, B * Q, 256)
         ready(self.group_end["heads"])
         # ---- the nine layers, last to first, each layer's own head gradient added in ----
-        dmem = zeros(B, pl.SN, 256) if seed_dmem is None else seed_dmem
-        dqpos_rows = zeros(B * Q, 256)
+        dmem = self._zeros(B, pl.SN, 256) if seed_dmem is None else seed_dmem
+        dqpos_rows = self._zeros(B * Q, 256)
         dx = self.dq_all[L - 1].clone()
         if seed_dq is not None:
             self._acc(dx, seed_dq)
@@ -344,7 +337,6 @@ class BaselineHeadGrad(SegmenterHeadGrad):
             raise RuntimeError("BaselineHeadGrad needs a CrossHeadBaseline")
         super().__init__(head, flat, base)
         self.rt = None
-        self._zeroed = False
         # the cross-attentions' backward: "keysplit" (0.61 against 1.67 ms at 16 700 keys, slower at
         # 1 050: 0.21 against 0.14; labnotes R23.4) or "mha_bwd"
         self.attn_bwd_algo = "keysplit"
@@ -360,11 +352,6 @@ class BaselineHeadGrad(SegmenterHeadGrad):
                            RelationTailGrad._layer_names("relation_decoder.layers.%d." % i)))
         groups.append(("rel_query", ["rel_query_feat.weight", "rel_query_embed.weight"]))
         return groups + SegmenterHeadGrad.param_groups(head)
-
-    def _zero_grads(self):
-        if not self._zeroed:            # (the parent's walk runs inside backward(): zeroed once)
-            self.flat_grad.zero_()
-        return self.grads
 
     # ------------------------------------------------------------------ forward with a tape
     @torch.no_grad()
@@ -449,21 +436,6 @@ class BaselineHeadGrad(SegmenterHeadGrad):
             got.append(t.contiguous())
         return got
 
-    def _lin_bwd_pad4(self, dy, x, W, grads, wname, bname):
-        """`_lin_bwd` for an output width that is no multiple of 4 (the GEMMs contract over
-        multiples of 4): zero columns / rows, as the parent does for `cls_embed`."""
-        M, n = dy.shape
-        npad = (n + 3) // 4 * 4
-        zeros = lambda *s_: torch.zeros(*s_, device=self.dev, dtype=torch.float32)
-        dyp, Wp = zeros(M, npad), zeros(npad, W.shape[1])
-        dyp[:, :n].copy_(dy)
-        Wp[:n].copy_(W)
-        gp = {"W": zeros(npad, W.shape[1]), "b": zeros(npad)}
-        dx = self._lin_bwd(dyp, x, Wp, gp, "W", "b")
-        self._acc(grads[wname], gp["W"][:n])
-        self._acc(grads[bname], gp["b"][:n])
-        return dx
-
     @torch.no_grad()
     @hip.on_device
     def backward(self, grads, on_ready=None, counts=None):
@@ -481,17 +453,16 @@ class BaselineHeadGrad(SegmenterHeadGrad):
         pl = self.dt["pl"]
         B, Q, R = pl.B, self.Q, self.R
         ready = on_ready if on_ready is not None else (lambda end: None)
-        zeros = lambda *s_: torch.zeros(*s_, device=self.dev, dtype=torch.float32)
         self._zeroed = False
         g = self._zero_grads()
         # ---- rel_cls_embed ----
         C = g_rel.shape[-1]
-        dr = self._lin_bwd_pad4(g_rel.view(B * R, C), rt["r_out"], w["rel_cls_embed.weight"], g,
-                                "rel_cls_embed.weight", "rel_cls_embed.bias")
+        dr = self._lin_bwd(g_rel.view(B * R, C), rt["r_out"], w["rel_cls_embed.weight"], g,
+                           "rel_cls_embed.weight", "rel_cls_embed.bias")
         ready(self.group_end["rel_cls_embed"])
         # ---- the two score products and the three normalisations (each backward is linear:
         # d r = class share + subject share + object share, in this order) ----
-        dq_rel = zeros(B * Q, 256)
+        dq_rel = self._zeros(B * Q, 256)
         for side, gs in (("sub", g_sub), ("obj", g_obj)):
             h1, e, hat = rt[side]
             dshare, de = E(B * R, 256), E(B * Q, 256)
@@ -508,8 +479,8 @@ class BaselineHeadGrad(SegmenterHeadGrad):
         self.dq_rel = dq_rel
         # ---- the six relation layers, last to first ----
         keysplit = self.attn_bwd_algo == "keysplit"
-        dmem = zeros(B, pl.SN, 256)
-        drpos_rows = zeros(B * R, 256)
+        dmem = self._zeros(B, pl.SN, 256)
+        drpos_rows = self._zeros(B * R, 256)
         scr = E(max([hip.mha_bwd_scratch_floats(B, R, R)] +
                     ([] if keysplit else [hip.mha_bwd_scratch_floats(B, R, n) for n in pl.N])))
         ks_scr = E(max(hip.mha_bwd_keysplit_scratch_floats(B, R, n) for n in pl.N)) \
@@ -683,7 +654,6 @@ class PSGTr2HeadGrad(SegmenterHeadGrad):
         rows = grads["mask_rows"].contiguous()
         M = int(rows.shape[0])
         ready = on_ready if on_ready is not None else (lambda end: None)
-        zeros = lambda *s_: torch.zeros(*s_, device=self.dev, dtype=torch.float32)
         g = self._zero_grads()
         me = st["mlp"][2]
         # ---- the two mask products with L = 2: subject rows, then object rows B * Q further on ----
@@ -704,7 +674,7 @@ class PSGTr2HeadGrad(SegmenterHeadGrad):
             dme_all = E(2 * N, 256)             # (a matched row appears once; failed rows match none)
             hip.scatter_rows_add(dme, rows2, dme_all, 1, 2 * N, 2 * M, 256)
         else:
-            dme_all = zeros(2 * N, 256)
+            dme_all = self._zeros(2 * N, 256)
         # ---- obj_mask_embed on all rows, the three class heads on the first half, post_norm ----
         dqn = self._mlp3_bwd(dme_all, st["qn"], st["mlp"], "obj_mask_embed", g)
         hip.tri_heads_bwd(
@@ -717,8 +687,8 @@ class PSGTr2HeadGrad(SegmenterHeadGrad):
         self.dq_all = dq_all.view(2, N, 256)
         ready(self.group_end["heads"])
         # ---- the nine layers, last to first, from the first half; no deep supervision ----
-        dmem = zeros(B, pl.SN, 256)
-        dqpos_rows = zeros(N, 256)
+        dmem = self._zeros(B, pl.SN, 256)
+        dqpos_rows = self._zeros(N, 256)
         dx = self._layers_bwd(self.dq_all[0].clone(), dqpos_rows, dmem, g, ready)
         hip.batch_sum(dx, g["query_feat.weight"], B)
         hip.batch_sum(self.dq_all[1], g["query_feat.weight"], B, accumulate=True)   # the stale masks
@@ -764,17 +734,11 @@ class SegPixelDecoderGrad(PixelDecoderGrad):
 
     def __init__(self, head, flat=None, base=0):
         super().__init__(head, flat, base)
-        self._zeroed = False
         self.dgrad_algo = "winograd4"   # the 3x3's data gradient: "winograd4" or "direct"
 
     @staticmethod
     def param_groups(head):
         return list(SegPixelDecoderGrad.BRANCH_GROUPS) + PixelDecoderGrad.param_groups(head)
-
-    def _zero_grads(self):
-        if not self._zeroed:            # (the parent's walk runs inside backward(): zeroed once)
-            self.flat_grad.zero_()
-        return self.grads
 
     # ------------------------------------------------------------------ forward with a tape
     @torch.no_grad()

@@ -60,8 +60,9 @@ from .flat_trainer import (MATRIX_LEARNER_REPACKED, FlatTrainer, refresh_encoder
                            refresh_key_positions, refresh_matrix_learner, refresh_q0,
                            refresh_query_positions, refresh_r0, refresh_relation_cross_attention,
                            refresh_resnet, refresh_self_attention, refresh_swin, step_lr)
-from .grad import (BackboneGrad, FfnDropout, HeadGrad, PixelDecoderGrad, RelationTailGrad,
-                   SwinBackboneGrad, SwinStagesGrad)
+from .backbone_grad import BackboneGrad, SwinBackboneGrad, SwinStagesGrad
+from .grad import FfnDropout, HeadGrad, RelationTailGrad
+from .pixel_grad import PixelDecoderGrad
 
 __all__ = ["TailTrainer", "step_lr", "segment_multipliers"]
 

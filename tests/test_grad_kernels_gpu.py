@@ -87,7 +87,7 @@ class _Tape:
         import types
         from pairnet_amd.grad import RelationTailGrad
         self.dev = torch.device(DEV)
-        self.head = types.SimpleNamespace(w=w or {})
+        self.head = self.backbone = types.SimpleNamespace(w=w or {})
         self.bn_scale = bn_scale or {}
         self._E = lambda *shape: RelationTailGrad._E(self, *shape)
 

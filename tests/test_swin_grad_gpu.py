@@ -153,7 +153,7 @@ def _check_stage(tape, oracle, x4, keep, report):
     c5 = tape.forward(x4.to(DEV), keep=keep)
     _compare("c5", c5.view(B, h * w, C), y, report)
     grads, dx = tape.backward(G.to(DEV).permute(0, 3, 1, 2), need_dx=True)
-    names = [n for _, ns in tape.param_groups(tape.head) for n in ns]
+    names = [n for _, ns in tape.param_groups(tape.backbone) for n in ns]
     assert set(names) == set(ref) and len(names) == 28
     for n in names:
         _compare(n, grads[n], ref[n], report)

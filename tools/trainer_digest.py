@@ -1,18 +1,18 @@
-"""SHA-256 digests of what the three training steps compute (pair-net_amd/train.py,
-baseline_train.py, bbox_train.py), for a bitwise A/B of two checkouts: the steps are reproducible
-bit for bit wherever no float atomic sits in the backward pass, so a change that is meant to leave
-them alone must leave these digests alone.  Public surface only, so the same file runs in an
-older checkout.  One configuration per GPU process, one JSON line each (fixed seeds, the tests'
-small fixtures): `names`, `seg_off` / `seg_lr` / `seg_wd`, `flat_p0` (as built); after three
-steps `flat_p` / `flat_m` / `flat_v` / `clip` / every returned value; `infer` (the head's inference
-outputs on the same input: the derived packs were refreshed); after `write_back()` the head's
-(and the backbone's) `state_dict()`.
+"""SHA-256 digests of what the four training steps compute (pair-net_amd/train.py,
+baseline_train.py, bbox_train.py, psgtr2_train.py), for a bitwise A/B of two checkouts: the steps
+are reproducible bit for bit wherever no float atomic sits in the backward pass, so a change that
+is meant to leave them alone must leave these digests alone.  Public surface only, so the same
+file runs in an older checkout.  One configuration per GPU process, one JSON line each (fixed
+seeds, the tests' small fixtures): `names`, `seg_off` / `seg_lr` / `seg_wd`, `flat_p0` (as built);
+after three steps `flat_p` / `flat_m` / `flat_v` / `clip` / every returned value; `infer` (the
+head's inference outputs on the same input: the derived packs were refreshed); after
+`write_back()` the head's (and the backbone's) `state_dict()`.
 
     python tools/trainer_digest.py [--out FILE] [--only tail,baseline_image] [--deterministic]
 
 `--deterministic` passes `deterministic=True` to the configurations with a pixel-decoder tape
 (PD_TAPE below): the deformable-attention backward then runs without float atomics
-(pn_msda_bwd_det_f32) and those six become reproducible too; the other six are built exactly as
+(pn_msda_bwd_det_f32) and those eight become reproducible too; the other six are built exactly as
 without the flag.
 
 Stops at the first configuration that fails or exceeds its time limit."""
@@ -28,10 +28,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 CONFIGS = ("tail", "tail_decoder", "tail_pixel_decoder", "tail_resnet", "tail_swin_last", "tail_swin_all_drop_path",
            "tail_device_targets", "tail_dropout", "baseline_feats", "baseline_image", "bbox_host",
-           "bbox_device_targets")
+           "bbox_device_targets", "triplet_feats", "triplet_image")
 # the configurations whose backward passes pn_msda_bwd_f32's float atomics (labnotes R27.3)
 PD_TAPE = ("tail_pixel_decoder", "tail_resnet", "tail_swin_last", "tail_swin_all_drop_path",
-           "baseline_feats", "baseline_image")
+           "baseline_feats", "baseline_image", "triplet_feats", "triplet_image")
 DEV = "cuda:0"
 
 
@@ -109,7 +109,7 @@ def run(name, deterministic=False):
             x = torch.randn(2, 3, H, W, generator=g).to(DEV)
         tr = P.TailTrainer(head, lr=1e-3, **kw, **det_kw)
         step = lambda: tr.step(x, metas, gt_rels, gt_labels, masks, point_coords=pts)
-    elif name.startswith("baseline"):
+    elif name.startswith(("baseline", "triplet")):     # the sibling heads, on the same small batch
         H, W = 64, 96
         cc = lambda w: dict(type="ClassificationCost", weight=w)
         tc = dict(num_points=256, oversample_ratio=3.0, importance_sample_ratio=0.75,
@@ -119,15 +119,20 @@ def run(name, deterministic=False):
                   sampler=dict(type="MaskPseudoSampler"),
                   id_assigner=dict(type="OldIdMatcher", sub_id_cost=cc(1.0), obj_id_cost=cc(1.0),
                                    r_cls_cost=cc(1.0)))
-        head = seeded_head(P.CrossHeadBaseline, P.baseline_head_cfg(), 1234, train_cfg=tc)
+        if name.startswith("baseline"):
+            head = seeded_head(P.CrossHeadBaseline, P.baseline_head_cfg(), 1234, train_cfg=tc)
+            trainer = P.BaselineTrainer
+        else:
+            head = seeded_head(P.PSGTrHead2, P.psgtr2_head_cfg(), 1234)
+            trainer = P.PSGTr2Trainer
         head.exact_mask_order = True
         x = pyramid(g, 2, H, W)
-        if name == "baseline_image":
+        if name.endswith("_image"):
             bb = P.ResNet50Hip().to(DEV)
             x = torch.randn(2, 3, H, W, generator=g).to(DEV)
         metas = [dict(img_shape=(H, W, 3), scale_factor=[1.5] * 4)] * 2
         masks = [(torch.rand(len(l), H // 2, W // 2, generator=g) > 0.6).to(torch.uint8) for l in gt_labels]
-        tr = P.BaselineTrainer(head, backbone=bb, lr=1e-3, seed=3, **det_kw)
+        tr = trainer(head, backbone=bb, lr=1e-3, seed=3, **det_kw)
         step = lambda: tr.step(x, metas, gt_rels, gt_labels, masks)
     else:
         H, W = 128, 160

@@ -5,7 +5,7 @@
             two launches, N = 200, widths 134 / 134 / 57) beside the COMPOSITION from the entries
             that were there before -- per head a zero-padded copy of the gradient and of the weight,
             two zero-filled padded gradient buffers, a row pad, a transpose, two GEMMs, a column sum
-            and three adds (`BaselineHeadGrad._lin_bwd_pad4` over `RelationTailGrad._lin_bwd`) --
+            and three adds (`Tape._lin_bwd` at a ragged output width) --
             both forms in the same run, alternating; and their largest difference;
   step      one `PSGTr2Trainer.step` from resident features and from the image (ResNet-50 stages 2-4
             trained), `masked_keysplit_min_keys` at its default, `deterministic` off and on
@@ -45,7 +45,7 @@ def psgtr2_head():
 
 
 def heads(args, res):
-    from pairnet_amd import BaselineHeadGrad, PSGTr2HeadGrad, hip
+    from pairnet_amd import PSGTr2HeadGrad, hip
     head = psgtr2_head()
     tape = PSGTr2HeadGrad(head)
     w = head.w
@@ -67,8 +67,8 @@ def heads(args, res):
 
     def composed():
         for dy, n in zip(d, names):
-            tape._acc(old_out["dqn"], BaselineHeadGrad._lin_bwd_pad4(
-                tape, dy, qn, w[n + ".weight"], old_out, n + ".weight", n + ".bias"))
+            tape._acc(old_out["dqn"], tape._lin_bwd(dy, qn, w[n + ".weight"], old_out, n + ".weight",
+                                                    n + ".bias"))
 
     old_out["dqn"].copy_(pre)
     new(), composed()
