@@ -16,6 +16,8 @@ class / mask logits of all nine decoder layers (needed by the training losses) a
 skips eight Q x H/4*W/4 mask GEMMs per image; `return_all_layers=True` reproduces the
 reference's (9, B, Q, ...) stacks.
 """
+import contextlib
+
 import torch
 
 from . import hip
@@ -54,6 +56,15 @@ class CrossHeadBaseline(CrossHead2):
         self._head_tape = None
         super().__init__(num_classes, in_channels, num_relations, num_obj_query=num_obj_query,
                          num_rel_query=num_rel_query, use_mask=use_mask, **kwargs)
+
+    @contextlib.contextmanager
+    def all_layers(self):
+        """`return_all_layers=True` for the forwards inside the block (what the losses read)."""
+        keep, self.return_all_layers = self.return_all_layers, True
+        try:
+            yield self
+        finally:
+            self.return_all_layers = keep
 
     # ------------------------------------------------------------------ params
     def param_shapes(self):

@@ -8,7 +8,7 @@ evaluator reads.  The backbone is SURVEY.md section 8 row a1 / (f)-2: the native
 one implementation per component: the PyTorch-ROCm / MIOpen ResNet-50 that bench.py times
 beside the native one lives in tools/torch_resnet50.py, not in the product package.
 """
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import contextlib
 import queue
@@ -383,6 +383,47 @@ class ResultStreamer:
         return self.head_i - self.tail_i
 
 
+def unpack_batch(data, need=("gt_masks",)):
+    """mmdet's collated `data_batch` dict -> (img, img_metas, gt_rels, gt_bboxes, gt_labels,
+    gt_masks): mmcv's DataContainers unwrapped (`.data`), the `[[...]]` single-element lists of a
+    one-GPU collate opened, `img` taken out of a one-element list.  img / img_metas / gt_rels /
+    gt_labels and the keys of `need` must be there (`KeyError`); the other two may be missing
+    (None)."""
+    unwrap = lambda v: getattr(v, "data", v)        # (mmcv DataContainer)
+    first = lambda v: v[0] if isinstance(v, (list, tuple)) and len(v) == 1 and \
+        isinstance(v[0], (list, tuple)) else v
+    need = ("img_metas", "gt_rels", "gt_labels") + tuple(need)
+    get = lambda k: first(unwrap(data[k] if k in need else data.get(k)))
+    img = unwrap(data["img"])
+    if isinstance(img, (list, tuple)):
+        img = img[0]
+    return (img,) + tuple(get(k) for k in ("img_metas", "gt_rels", "gt_bboxes", "gt_labels",
+                                           "gt_masks"))
+
+
+def parse_losses(out, num_samples):
+    """mmdet's `_parse_losses` on a step's dict of scalars: dict(loss, log_vars, num_samples) with
+    `loss` = the sum of the terms whose name contains "loss" and `log_vars` every entry (and
+    `loss`) as a float."""
+    loss = sum(v for k, v in out.items() if "loss" in k)
+    return dict(loss=loss, log_vars={k: float(v) for k, v in list(out.items()) + [("loss", loss)]},
+                num_samples=num_samples)
+
+
+# The training entries, one row per trainer class (runner.py builds its tables from these rows):
+# the head it trains, the detector's step entry, the attribute that keeps the trainer, its builder,
+# and whether the step takes ground-truth masks (else: boxes, on `extract_feat`'s features).
+TrainEntry = namedtuple("TrainEntry", "head step slot builder masks")
+TRAIN_ENTRIES = {
+    "TailTrainer": TrainEntry("CrossHead2", "train_step", "_trainer", "trainer", True),
+    "BaselineTrainer": TrainEntry("CrossHeadBaseline", "full_train_step", "_full_trainer",
+                                  "full_trainer", True),
+    "BBoxTrainer": TrainEntry("CrossHeadBBox", "box_train_step", "_box_trainer", "box_trainer",
+                              False),
+    "PSGTr2Trainer": TrainEntry("PSGTrHead2", "triplet_train_step", "_triplet_trainer",
+                                "triplet_trainer", True)}
+
+
 class PSGTr:
     """`PSGTr(SingleStageDetector)` of the reference, inference half."""
 
@@ -524,27 +565,30 @@ class PSGTr:
                                          gt_bboxes_ignore, **kw)
 
     @torch.no_grad()
+    def _val_head_losses(self, method_name, all_layers, refusal, img, img_metas, lead, gt_labels,
+                         gt_masks, kw):
+        """What `val_seg_losses`, `val_full_losses` and `val_triplet_losses` share: extract_feat ->
+        prepared ground-truth masks -> head forward (with all decoder layers where the loss reads
+        them) -> the head's `method_name(*outs, *lead, gt_labels, gt_masks, img_metas, **kw)`."""
+        head = self.bbox_head
+        if not hasattr(head, method_name):
+            raise NotImplementedError(refusal % type(head).__name__)
+        x = self.extract_feat(img)
+        gt_masks = self._prepare_gt_masks(img, gt_masks)
+        with head.all_layers() if all_layers else contextlib.nullcontext():
+            outs = head.forward(x, img_metas)
+        return getattr(head, method_name)(*outs, *lead, gt_labels, gt_masks, img_metas, **kw)
+
     def val_seg_losses(self, img, img_metas, gt_labels, gt_masks, **kw):
         """The Mask2Former segmentation losses of a head that has them (`CrossHeadBaseline.seg_losses`:
         per-decoder-layer loss_cls / loss_mask / loss_dice, relation_heads/baseline.py:588-653) as
         validation values: extract_feat -> ground-truth masks prepared as in `forward_train`
         (psgtr.py:126-141) -> head forward with all decoder layers -> `seg_losses`.  Keywords go to
         `Mask2FormerLoss.loss` (`grads={}`, `points=`, `seed=`, `step=`, `num_total_masks=`)."""
-        head = self.bbox_head
-        if not hasattr(head, "seg_losses"):
-            raise NotImplementedError("%s has no segmentation losses here (CrossHeadBaseline does)"
-                                      % type(head).__name__)
-        x = self.extract_feat(img)
-        gt_masks = self._prepare_gt_masks(img, gt_masks)
-        old = head.return_all_layers
-        head.return_all_layers = True
-        try:
-            outs = head.forward(x, img_metas)
-        finally:
-            head.return_all_layers = old
-        return head.seg_losses(*outs, gt_labels, gt_masks, img_metas, **kw)
+        return self._val_head_losses(
+            "seg_losses", True, "%s has no segmentation losses here (CrossHeadBaseline does)",
+            img, img_metas, (), gt_labels, gt_masks, kw)
 
-    @torch.no_grad()
     def val_full_losses(self, img, img_metas, gt_rels, gt_labels, gt_masks, **kw):
         """The whole loss dict of a head that has it (`CrossHeadBaseline.full_losses`: the 3 L
         segmentation terms plus r_loss_cls, loss_subject_match and loss_object_match,
@@ -552,35 +596,19 @@ class PSGTr:
         extract_feat -> prepared ground-truth masks -> head forward with all decoder layers ->
         `full_losses`.  Keywords as `val_seg_losses`; `grads={}` also receives the relation logits'
         gradients."""
-        head = self.bbox_head
-        if not hasattr(head, "full_losses"):
-            raise NotImplementedError("%s has no full loss dict here (CrossHeadBaseline does)"
-                                      % type(head).__name__)
-        x = self.extract_feat(img)
-        gt_masks = self._prepare_gt_masks(img, gt_masks)
-        old = head.return_all_layers
-        head.return_all_layers = True
-        try:
-            outs = head.forward(x, img_metas)
-        finally:
-            head.return_all_layers = old
-        return head.full_losses(*outs, gt_rels, None, gt_labels, gt_masks, img_metas, **kw)
+        return self._val_head_losses(
+            "full_losses", True, "%s has no full loss dict here (CrossHeadBaseline does)",
+            img, img_metas, (gt_rels, None), gt_labels, gt_masks, kw)
 
-    @torch.no_grad()
     def val_triplet_losses(self, img, img_metas, gt_rels, gt_labels, gt_masks, **kw):
         """The loss dict of a head that matches triplets (`PSGTrHead2.triplet_losses`: s_loss_cls,
         o_loss_cls, r_loss_cls and the mask / dice terms of both sides,
         relation_heads/psgtr_head2.py:447-594) as validation values, shaped like `val_full_losses`:
         extract_feat -> prepared ground-truth masks -> head forward -> `triplet_losses`.  Keywords
         go to `PSGTrHead2Loss.loss` (`grads={}`, `points=`, `seed=`, `step=`, `num_total_masks=`)."""
-        head = self.bbox_head
-        if not hasattr(head, "triplet_losses"):
-            raise NotImplementedError("%s has no triplet loss dict here (PSGTrHead2 does)"
-                                      % type(head).__name__)
-        x = self.extract_feat(img)
-        gt_masks = self._prepare_gt_masks(img, gt_masks)
-        outs = head.forward(x, img_metas)
-        return head.triplet_losses(*outs, gt_rels, None, gt_labels, gt_masks, img_metas, **kw)
+        return self._val_head_losses(
+            "triplet_losses", False, "%s has no triplet loss dict here (PSGTrHead2 does)",
+            img, img_metas, (gt_rels, None), gt_labels, gt_masks, kw)
 
     def _prepare_gt_masks(self, img, gt_masks):
         """PSGTr.forward_train's ground-truth mask preparation (psgtr.py:126-141): zero-pad to the
@@ -687,28 +715,48 @@ class PSGTr:
         tensor, nearest half-size), then `trainer().step` runs -- the trainer built by an earlier
         `trainer(...)` call if there is one (e.g. `trainer(dropout=True)` for the reference's
         train-mode FFN dropout), else the default, deterministic one."""
+        return self._train_step("TailTrainer", img, img_metas, gt_rels, gt_bboxes, gt_labels,
+                                gt_masks, point_coords=point_coords)
+
+    def _train_step(self, trainer, img, img_metas, gt_rels, gt_bboxes, gt_labels, gt_masks=None,
+                    **kw):
+        """The four `*train_step` entries: the row of `TRAIN_ENTRIES` named `trainer` says where
+        the trainer is kept, what builds the default one and which of the two paths runs -- the
+        prepared masks, then the image or its features according to `tr.backbone` (the three mask
+        heads; `kw` goes to `step`), or `extract_feat` and the boxes (the box head).  `img` as a
+        dict is mmdet's form (`unpack_batch`, `parse_losses`)."""
+        row = TRAIN_ENTRIES[trainer]
         mmdet_form = isinstance(img, dict)
         if mmdet_form:
-            data = img
-            unwrap = lambda v: getattr(v, "data", v)        # (mmcv DataContainer)
-            first = lambda v: v[0] if isinstance(v, (list, tuple)) and len(v) == 1 and \
-                isinstance(v[0], (list, tuple)) else v
-            img = unwrap(data["img"])
-            if isinstance(img, (list, tuple)):
-                img = img[0]
-            img_metas = first(unwrap(data["img_metas"]))
-            gt_rels, gt_labels = first(unwrap(data["gt_rels"])), first(unwrap(data["gt_labels"]))
-            gt_masks = first(unwrap(data["gt_masks"]))
-            gt_bboxes = first(unwrap(data.get("gt_bboxes")))
-        tr = getattr(self, "_trainer", None) or self.trainer()
-        gt_masks = self._prepare_gt_masks(img, gt_masks)
-        x = img if tr.backbone is not None else self.extract_feat(img)
-        out = tr.step(x, img_metas, gt_rels, gt_labels, gt_masks, point_coords=point_coords)
-        if not mmdet_form:
-            return out
-        loss = sum(v for k, v in out.items() if "loss" in k)
-        return dict(loss=loss, log_vars={k: float(v) for k, v in list(out.items()) + [("loss", loss)]},
-                    num_samples=len(img_metas))
+            img, img_metas, gt_rels, gt_bboxes, gt_labels, gt_masks = unpack_batch(
+                img, need=("gt_masks",) if row.masks else ("gt_bboxes",))
+        tr = getattr(self, row.slot, None) or getattr(self, row.builder)()
+        if row.masks:
+            gt_masks = self._prepare_gt_masks(img, gt_masks)
+            x = img if tr.backbone is not None else self.extract_feat(img)
+            out = tr.step(x, img_metas, gt_rels, gt_labels, gt_masks, **kw)
+        else:
+            out = tr.step(self.extract_feat(img), img_metas, gt_rels, gt_bboxes, gt_labels)
+        return parse_losses(out, len(img_metas)) if mmdet_form else out
+
+    def _resnet_trainer(self, head_cls, trainer_cls, name, slot, others, train_backbone, kw):
+        """`full_trainer` / `triplet_trainer`: a trainer of `trainer_cls` over `head_cls` and, by
+        `train_backbone`, a ResNet backbone's stages 2-4, kept in `slot`; `name` and `others` (the
+        builders of the other heads) go into the refusals."""
+        train_backbone = self._forward_only_backbone(train_backbone)
+        if type(self.bbox_head) is not head_cls:
+            raise NotImplementedError("%s is built for %s only (%s: %s)" % (
+                name, head_cls.__name__, type(self.bbox_head).__name__, others))
+        resnet = isinstance(self.backbone, ResNet50Hip)
+        if train_backbone is None:
+            train_backbone = resnet
+        if train_backbone and not resnet:
+            raise NotImplementedError("%s trains a ResNet50Hip backbone; a %s backbone is out of "
+                                      "scope (train_backbone=False keeps it frozen)"
+                                      % (name, type(self.backbone).__name__))
+        tr = trainer_cls(self.bbox_head, backbone=self.backbone if train_backbone else None, **kw)
+        setattr(self, slot, tr)
+        return tr
 
     def full_trainer(self, train_backbone=None, **kw):
         """`trainer()` for the sibling head: builds and keeps a `pairnet_amd.BaselineTrainer` over
@@ -719,22 +767,9 @@ class PSGTr:
         `BaselineTrainer` (lr, lr_mult, decay_mult, seed, masked_keysplit_min_keys,
         `deterministic=True` for a bitwise reproducible step without float atomics).  `trainer()`,
         `train_step()` and `val_losses()` keep refusing this head."""
-        from .backbone import ResNet50Hip
         from .baseline_train import BaselineTrainer
-        train_backbone = self._forward_only_backbone(train_backbone)
-        if type(self.bbox_head) is not CrossHeadBaseline:
-            raise NotImplementedError("full_trainer is built for CrossHeadBaseline only (%s: "
-                                      "trainer())" % type(self.bbox_head).__name__)
-        resnet = isinstance(self.backbone, ResNet50Hip)
-        if train_backbone is None:
-            train_backbone = resnet
-        if train_backbone and not resnet:
-            raise NotImplementedError("full_trainer trains a ResNet50Hip backbone; a %s backbone is "
-                                      "out of scope (train_backbone=False keeps it frozen)"
-                                      % type(self.backbone).__name__)
-        self._full_trainer = BaselineTrainer(self.bbox_head,
-                                             backbone=self.backbone if train_backbone else None, **kw)
-        return self._full_trainer
+        return self._resnet_trainer(CrossHeadBaseline, BaselineTrainer, "full_trainer",
+                                    "_full_trainer", "trainer()", train_backbone, kw)
 
     def full_train_step(self, img, img_metas=None, gt_rels=None, gt_bboxes=None, gt_labels=None,
                         gt_masks=None, num_total_masks=None):
@@ -743,27 +778,8 @@ class PSGTr:
         `(data_batch, optimizer)` -> mmdet's dict(loss, log_vars, num_samples) with `loss` the sum
         of the terms whose name contains "loss".  Runs `full_trainer().step` -- the trainer an
         earlier `full_trainer(...)` call built if there is one, else the default one."""
-        mmdet_form = isinstance(img, dict)
-        if mmdet_form:
-            data = img
-            unwrap = lambda v: getattr(v, "data", v)        # (mmcv DataContainer)
-            first = lambda v: v[0] if isinstance(v, (list, tuple)) and len(v) == 1 and \
-                isinstance(v[0], (list, tuple)) else v
-            img = unwrap(data["img"])
-            if isinstance(img, (list, tuple)):
-                img = img[0]
-            img_metas = first(unwrap(data["img_metas"]))
-            gt_rels, gt_labels = first(unwrap(data["gt_rels"])), first(unwrap(data["gt_labels"]))
-            gt_masks = first(unwrap(data["gt_masks"]))
-        tr = getattr(self, "_full_trainer", None) or self.full_trainer()
-        gt_masks = self._prepare_gt_masks(img, gt_masks)
-        x = img if tr.backbone is not None else self.extract_feat(img)
-        out = tr.step(x, img_metas, gt_rels, gt_labels, gt_masks, num_total_masks=num_total_masks)
-        if not mmdet_form:
-            return out
-        loss = sum(v for k, v in out.items() if "loss" in k)
-        return dict(loss=loss, log_vars={k: float(v) for k, v in list(out.items()) + [("loss", loss)]},
-                    num_samples=len(img_metas))
+        return self._train_step("BaselineTrainer", img, img_metas, gt_rels, gt_bboxes, gt_labels,
+                                gt_masks, num_total_masks=num_total_masks)
 
     def triplet_trainer(self, train_backbone=None, **kw):
         """`trainer()` for the triplet head: builds and keeps a `pairnet_amd.PSGTr2Trainer` over
@@ -774,24 +790,9 @@ class PSGTr:
         `PSGTr2Trainer` (lr, lr_mult, decay_mult, seed, masked_keysplit_min_keys,
         `deterministic=True` for a bitwise reproducible step without float atomics).  `trainer()`,
         `train_step()` and the other heads' `val_*losses()` keep refusing this head."""
-        from .backbone import ResNet50Hip
         from .psgtr2_train import PSGTr2Trainer
-        train_backbone = self._forward_only_backbone(train_backbone)
-        if type(self.bbox_head) is not PSGTrHead2:
-            raise NotImplementedError("triplet_trainer is built for PSGTrHead2 only (%s: trainer() / "
-                                      "full_trainer() / box_trainer())"
-                                      % type(self.bbox_head).__name__)
-        resnet = isinstance(self.backbone, ResNet50Hip)
-        if train_backbone is None:
-            train_backbone = resnet
-        if train_backbone and not resnet:
-            raise NotImplementedError("triplet_trainer trains a ResNet50Hip backbone; a %s backbone "
-                                      "is out of scope (train_backbone=False keeps it frozen)"
-                                      % type(self.backbone).__name__)
-        self._triplet_trainer = PSGTr2Trainer(self.bbox_head,
-                                              backbone=self.backbone if train_backbone else None,
-                                              **kw)
-        return self._triplet_trainer
+        return self._resnet_trainer(PSGTrHead2, PSGTr2Trainer, "triplet_trainer", "_triplet_trainer",
+                                    "trainer() / full_trainer() / box_trainer()", train_backbone, kw)
 
     def triplet_train_step(self, img, img_metas=None, gt_rels=None, gt_bboxes=None, gt_labels=None,
                            gt_masks=None, num_total_masks=None):
@@ -801,27 +802,8 @@ class PSGTr:
         with `loss` the sum of the terms whose name contains "loss".  Runs `triplet_trainer().step`
         -- the trainer an earlier `triplet_trainer(...)` call built if there is one, else the
         default one."""
-        mmdet_form = isinstance(img, dict)
-        if mmdet_form:
-            data = img
-            unwrap = lambda v: getattr(v, "data", v)        # (mmcv DataContainer)
-            first = lambda v: v[0] if isinstance(v, (list, tuple)) and len(v) == 1 and \
-                isinstance(v[0], (list, tuple)) else v
-            img = unwrap(data["img"])
-            if isinstance(img, (list, tuple)):
-                img = img[0]
-            img_metas = first(unwrap(data["img_metas"]))
-            gt_rels, gt_labels = first(unwrap(data["gt_rels"])), first(unwrap(data["gt_labels"]))
-            gt_masks = first(unwrap(data["gt_masks"]))
-        tr = getattr(self, "_triplet_trainer", None) or self.triplet_trainer()
-        gt_masks = self._prepare_gt_masks(img, gt_masks)
-        x = img if tr.backbone is not None else self.extract_feat(img)
-        out = tr.step(x, img_metas, gt_rels, gt_labels, gt_masks, num_total_masks=num_total_masks)
-        if not mmdet_form:
-            return out
-        loss = sum(v for k, v in out.items() if "loss" in k)
-        return dict(loss=loss, log_vars={k: float(v) for k, v in list(out.items()) + [("loss", loss)]},
-                    num_samples=len(img_metas))
+        return self._train_step("PSGTr2Trainer", img, img_metas, gt_rels, gt_bboxes, gt_labels,
+                                gt_masks, num_total_masks=num_total_masks)
 
     def box_trainer(self, **kw):
         """`trainer()` for the box head: builds and keeps a `pairnet_amd.BBoxTrainer` over the
@@ -844,25 +826,7 @@ class PSGTr:
         optimizer)` -> mmdet's dict(loss, log_vars, num_samples).  Backbone and neck run as in
         inference (frozen: the reference's graph does not reach them), then `box_trainer().step`
         -- the trainer an earlier `box_trainer(...)` call built if there is one."""
-        mmdet_form = isinstance(img, dict)
-        if mmdet_form:
-            data = img
-            unwrap = lambda v: getattr(v, "data", v)        # (mmcv DataContainer)
-            first = lambda v: v[0] if isinstance(v, (list, tuple)) and len(v) == 1 and \
-                isinstance(v[0], (list, tuple)) else v
-            img = unwrap(data["img"])
-            if isinstance(img, (list, tuple)):
-                img = img[0]
-            img_metas = first(unwrap(data["img_metas"]))
-            gt_rels, gt_labels = first(unwrap(data["gt_rels"])), first(unwrap(data["gt_labels"]))
-            gt_bboxes = first(unwrap(data["gt_bboxes"]))
-        tr = getattr(self, "_box_trainer", None) or self.box_trainer()
-        out = tr.step(self.extract_feat(img), img_metas, gt_rels, gt_bboxes, gt_labels)
-        if not mmdet_form:
-            return out
-        loss = sum(v for k, v in out.items() if "loss" in k)
-        return dict(loss=loss, log_vars={k: float(v) for k, v in list(out.items()) + [("loss", loss)]},
-                    num_samples=len(img_metas))
+        return self._train_step("BBoxTrainer", img, img_metas, gt_rels, gt_bboxes, gt_labels)
 
     @torch.no_grad()
     def val_box_losses(self, img, img_metas, gt_rels, gt_bboxes, gt_labels, **kw):

@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .detector import load_checkpoint
+from .detector import TRAIN_ENTRIES, load_checkpoint
 
 __all__ = ["EpochRunner", "TrainLog", "save_checkpoint", "resume", "epoch_order",
            "auto_scaled_lr", "CHECKPOINT_VERSION"]
@@ -46,13 +46,10 @@ __all__ = ["EpochRunner", "TrainLog", "save_checkpoint", "resume", "epoch_order"
 CHECKPOINT_VERSION = "pairnet_amd-ckpt-1"
 DEFAULT_SEED = 10086        # tools/train.py:204 hard-codes it
 
+# two views of the detector's table (detector.TRAIN_ENTRIES, one row per trainer):
 # trainer class -> (the detector's step entry, where the detector keeps the trainer, its builder)
-ENTRIES = {"TailTrainer": ("train_step", "_trainer", "trainer"),
-           "BaselineTrainer": ("full_train_step", "_full_trainer", "full_trainer"),
-           "BBoxTrainer": ("box_train_step", "_box_trainer", "box_trainer"),
-           "PSGTr2Trainer": ("triplet_train_step", "_triplet_trainer", "triplet_trainer")}
-HEAD_TRAINER = {"CrossHead2": "TailTrainer", "CrossHeadBaseline": "BaselineTrainer",
-                "CrossHeadBBox": "BBoxTrainer", "PSGTrHead2": "PSGTr2Trainer"}
+ENTRIES = {name: (row.step, row.slot, row.builder) for name, row in TRAIN_ENTRIES.items()}
+HEAD_TRAINER = {row.head: name for name, row in TRAIN_ENTRIES.items()}
 
 
 # ---------------------------------------------------------------------------- checkpoints
@@ -115,11 +112,9 @@ def _restore(det, filename, trainer_kw):
                       % (len(own - keys), sorted(own - keys)[:2], len(unexpected),
                          sorted(unexpected)[:2]))
     kw = dict(trainer_kw)
-    from . import baseline_train, bbox_train, psgtr2_train, train
-    classes = {c.__name__: c for c in (train.TailTrainer, baseline_train.BaselineTrainer,
-                                       bbox_train.BBoxTrainer, psgtr2_train.PSGTr2Trainer)}
-    if block["class"] in classes:         # (any other class: `_build_trainer` refuses it by name)
-        accepted = inspect.signature(classes[block["class"]].__init__).parameters
+    from . import api
+    if block["class"] in ENTRIES:         # (any other class: `_build_trainer` refuses it by name)
+        accepted = inspect.signature(getattr(api, block["class"]).__init__).parameters
         for key in ("deterministic", "device_targets", "seed"):
             if key in accepted and key in block:
                 kw.setdefault(key, block[key])
@@ -418,8 +413,8 @@ class EpochRunner:
         if name not in ENTRIES:
             raise ValueError("no training step for a %s" % name)
         self.trainer = trainer
-        self._entry, attr, _ = ENTRIES[name]
-        setattr(self.det, attr, trainer)          # the detector's step entry runs THIS trainer
+        self._row = TRAIN_ENTRIES[name]
+        setattr(self.det, self._row.slot, trainer)     # the detector's step entry runs THIS trainer
 
     def _prepare(self):
         """`load_from` / `resume_from`, then the trainer; returns the meta to start from."""
@@ -465,11 +460,9 @@ class EpochRunner:
         raise RuntimeError("no crop kept a relation in 100 draws (samples %s)" % idx)
 
     def _step(self, b):
-        fn = getattr(self.det, self._entry)
-        if self._entry == "box_train_step":
-            return fn(b["img"], b["img_metas"], b["gt_rels"], b.get("gt_bboxes"), b["gt_labels"])
-        return fn(b["img"], b["img_metas"], b["gt_rels"], b.get("gt_bboxes"), b["gt_labels"],
-                  b.get("gt_masks"))
+        masks = (b.get("gt_masks"),) if self._row.masks else ()
+        return getattr(self.det, self._row.step)(b["img"], b["img_metas"], b["gt_rels"],
+                                                 b.get("gt_bboxes"), b["gt_labels"], *masks)
 
     def train_epoch(self, epoch, flush=True):
         """One epoch (0-based).  `flush=False` leaves the log's records in flight -- the loop then
